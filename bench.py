@@ -3,11 +3,16 @@
 Adam on both), BASELINE.json's metric, on synthetic CelebA-shaped batches.
 
   python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                               (also the per-kernel table / roofline, per-step spread, CPU baseline)
+  python bench.py ... --dump-outputs DIR                   (what the last timed step computed, as DIR/<name>.npy)
 
 N=1 workload = BASELINE.json configs[1]: CelebA 64x64 RGB, batch 256, blur sigma schedule on
 (BlurDecayController(max_value=5) -> 31 taps), 64-arch (build-side definition).
 N>1 = configs[2]: the same per-GPU work, batch 256 x N sharded data-parallel, RCCL SUM all-reduce of the
 critic and generator gradients ("weak" scaling).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line; everything else it can report (the per-kernel HIP-event
+table and roofline from extra un-timed steps, the per-step spread, the CPU baseline) is measured only under --full.
 """
 from __future__ import annotations
 
@@ -203,6 +208,26 @@ def hbm_traffic(kernel, arch, batch):
     return None
 
 
+DUMP_MAX_ELEMS = 1 << 22        # per array: 16 MB of fp32; larger outputs are written as a fixed, seeded sample of their elements
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (name, tensor) as out_dir/<name>.npy, float32 (float64 kept).  An array of more than DUMP_MAX_ELEMS
+    elements is written as the elements at a sorted random index set drawn from a generator seeded by the array's size alone, so
+    that two builds run with the same arguments write the same positions.  At most 4 x 16 MB for a step, 16 MB for blur256."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays:
+        a = t.detach().reshape(-1).cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t).reshape(-1)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size == 0:
+            continue                        # e.g. the state of a model without batch norm
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(a.size).permutation(a.size)[:DUMP_MAX_ELEMS])
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def bench_blur(args):
     """BASELINE.json configs[4] (C5), one rank's share: 64 synthetic 256x256x3 images, a step = the 7 blur applications of one
     training step (D-step forward x3, blur^T, GP second order; G-step forward, blur^T) at the given sigma
@@ -238,53 +263,59 @@ def bench_blur(args):
     dist.barrier()
     torch.cuda.synchronize()
     dt = dist.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and dist.rank() == 0:
+        # the last application of the last timed step wrote y (apps is odd: the ping-pong ends on x -> y)
+        dump_outputs(args.dump_outputs, [("blurred", y if apps % 2 else x)])
     dp_evidence = dist.evidence()
     alg_bytes = 8.0 * B * H * W * C                              # per application
     value = alg_bytes * apps * args.steps * world / dt / 1e9
-    ops.prof_reset()
-    ops.prof_enable(True)
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    recs = ops.prof_records(with_exec=True)
-    ops.prof_enable(False)
-    ops.prof_reset()
-    kern = {}
-    exec_fl = 0.0
-    for name, ms, fl, by, ex in recs:
-        k = kern.setdefault(name, [0, 0.0])
-        k[0] += 1; k[1] += ms
-        exec_fl += ex if name.startswith(("blur_band", "blur_panel")) else 0.0
-    total_ms = sum(k[1] for k in kern.values())
-    per_app_ms = total_ms / (3 * apps)
-    ach = alg_bytes / (per_app_ms * 1e-3) / 1e9
-    # at wide kernels the banded Toeplitz product on the fp32 matrix pipe is the binding roof, not HBM: report both
-    dom = max(kern, key=lambda n: kern[n][1])
-    roof = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(ach / PEAK_HBM_GBS, 4),
-            "traffic": hbm_traffic(f"blur{nt}", "blur256", B), "algorithmic_bytes_per_launch": round(alg_bytes),
-            "launches_per_application": len(recs) // (3 * apps), "avg_application_ms": round(per_app_ms, 5),
-            "kernels_ms_per_application": {n: round(k[1] / (3 * apps), 5) for n, k in kern.items()}}
-    if exec_fl > 0:
-        # above 65 taps the banded Toeplitz products (both passes of the 32-row panel kernel in one launch; the two transposing
-        # band passes for other channel counts) run on the fp32 matrix pipe and THAT is the binding roof: the flops they issue
-        # (every 32x32x2 MFMA of the bands, image-clipped) over their own durations.
-        # The HBM view of the same launches stays in the object as "hbm".
-        tf = exec_fl / (total_ms * 1e-3) / 1e12
-        hbm_view = {k: roof[k] for k in ("achieved", "peak", "unit", "frac")}
-        roof.update({"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_MFMA_F32_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(tf / PEAK_MFMA_F32_TFLOPS, 4), "issued_gflop_per_application": round(exec_fl / (3 * apps) / 1e9, 3),
-                     "time_at_peak_ms_per_application": round(exec_fl / (3 * apps) / (PEAK_MFMA_F32_TFLOPS * 1e12) * 1e3, 5),
-                     "hbm": hbm_view})
+    roof = None
+    if args.full:
+        ops.prof_reset()
+        ops.prof_enable(True)
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        recs = ops.prof_records(with_exec=True)
+        ops.prof_enable(False)
+        ops.prof_reset()
+        kern = {}
+        exec_fl = 0.0
+        for name, ms, fl, by, ex in recs:
+            k = kern.setdefault(name, [0, 0.0])
+            k[0] += 1; k[1] += ms
+            exec_fl += ex if name.startswith(("blur_band", "blur_panel")) else 0.0
+        total_ms = sum(k[1] for k in kern.values())
+        per_app_ms = total_ms / (3 * apps)
+        ach = alg_bytes / (per_app_ms * 1e-3) / 1e9
+        # at wide kernels the banded Toeplitz product on the fp32 matrix pipe is the binding roof, not HBM: report both
+        dom = max(kern, key=lambda n: kern[n][1])
+        roof = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(ach / PEAK_HBM_GBS, 4),
+                "traffic": hbm_traffic(f"blur{nt}", "blur256", B), "algorithmic_bytes_per_launch": round(alg_bytes),
+                "launches_per_application": len(recs) // (3 * apps), "avg_application_ms": round(per_app_ms, 5),
+                "kernels_ms_per_application": {n: round(k[1] / (3 * apps), 5) for n, k in kern.items()}}
+        if exec_fl > 0:
+            # above 65 taps the banded Toeplitz products (both passes of the 32-row panel kernel in one launch; the two transposing
+            # band passes for other channel counts) run on the fp32 matrix pipe and THAT is the binding roof: the flops they issue
+            # (every 32x32x2 MFMA of the bands, image-clipped) over their own durations.
+            # The HBM view of the same launches stays in the object as "hbm".
+            tf = exec_fl / (total_ms * 1e-3) / 1e12
+            hbm_view = {k: roof[k] for k in ("achieved", "peak", "unit", "frac")}
+            roof.update({"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_MFMA_F32_TFLOPS, "unit": "TFLOP/s",
+                         "frac": round(tf / PEAK_MFMA_F32_TFLOPS, 4), "issued_gflop_per_application": round(exec_fl / (3 * apps) / 1e9, 3),
+                         "time_at_peak_ms_per_application": round(exec_fl / (3 * apps) / (PEAK_MFMA_F32_TFLOPS * 1e12) * 1e3, 5),
+                         "hbm": hbm_view})
     if dist.rank() == 0:
         out = {"metric": "blur GB/s (8*H*W*C bytes per image per application, 7 applications per step)", "value": round(value, 1),
                "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": f"blur256: {B}x{H}x{W}x{C} per GPU, sigma {args.sigma} ({nt} taps), {apps} blur applications per step",
-                          "global_batch": B * world, "parallelism": f"dp{world}"},
-               "roofline": roof}
+                          "global_batch": B * world, "parallelism": f"dp{world}"}}
+        if roof is not None:
+            out["roofline"] = roof
         if dp_evidence:
             out["dp"] = dp_evidence
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_blur(B, H, W, C, args.sigma, apps)
         print(json.dumps(out), flush=True)
     dist.barrier()
@@ -301,11 +332,18 @@ def main():
     ap.add_argument("--sigma", type=float, default=None, help="blur sigma (default: the demos' schedule start: 5 for CelebA, 0.05 for MNIST)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: the GLOBAL batch stays 2048 (BASELINE.json configs[2]) and is "
                     "split over the ranks, instead of 256 images per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: the per-kernel HIP-event table and roofline (extra "
+                    "un-timed steps), the per-step spread and the CPU baseline (off: the line carries the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(step metrics and updated weights; blur256: the blurred images) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave the per-kernel table and roofline out")
     ap.add_argument("--cpu-sample-batch", type=int, default=None, help="batch of the CPU baseline (default: the GPU line's batch)")
-    ap.add_argument("--kernels-out", default=None, help="write the full per-kernel table (and one step's launch sequence) to this JSON file")
+    ap.add_argument("--kernels-out", default=None, help="with --full: write the full per-kernel table (and one step's launch sequence) "
+                    "to this JSON file")
     args = ap.parse_args()
+    if args.kernels_out and not (args.full and not args.no_profile):
+        ap.error("--kernels-out needs --full (and no --no-profile)")
     if args.sigma is None:
         args.sigma = 0.05 if args.arch == "mnist" else 5.0      # demo_mnist.py:199 (initial_blur_std), demo_celeba.py:226
 
@@ -348,34 +386,46 @@ def main():
 
     def step():
         ctl.on_batch_begin(0, {})
-        gan.train_on_batch(reals)
+        return gan.train_on_batch(reals)
 
     for _ in range(args.warmup):
         step()
     dist.barrier()
     torch.cuda.synchronize()
-    # one event per step on the launch stream (a marker packet per 100+ kernel launches): the spread of the per-step times says
-    # whether `value` -- the mean over a region of a few hundred milliseconds -- carries a host hiccup of the shared box
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # --full: one event per step on the launch stream (a marker packet per 100+ kernel launches): the spread of the per-step times
+    # says whether `value` -- the mean over a region of a few hundred milliseconds -- carries a host hiccup of the shared box
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
+    metrics = None
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     for i in range(args.steps):
-        step()
-        marks[i + 1].record()
+        metrics = step()
+        if marks:
+            marks[i + 1].record()
     dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dt = dist.max_over_ranks(dt)
     value = B * world * args.steps / dt
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    step_ms = {"p10": round(per_step[len(per_step) // 10], 4), "p50": round(per_step[len(per_step) // 2], 4),
-               "p90": round(per_step[(len(per_step) * 9) // 10], 4), "max": round(per_step[-1], 4)} if per_step else None
+    if args.dump_outputs and dist.rank() == 0:
+        # what a caller of train_on_batch gets from the last timed step: its metrics, and both models as that step left them
+        outs = [("metrics", torch.tensor(metrics if metrics is not None else [], dtype=torch.float64))]
+        for name, model in (("generator", gan.generator), ("discriminator", gan.discriminator)):
+            s = model.store
+            outs += [(f"{name}_weights", s.theta[:s.n_train]), (f"{name}_state", s.state[:s.n_state])]
+        dump_outputs(args.dump_outputs, outs)
+    step_ms = None
+    if marks and args.steps:
+        per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+        step_ms = {"p10": round(per_step[len(per_step) // 10], 4), "p50": round(per_step[len(per_step) // 2], 4),
+                   "p90": round(per_step[(len(per_step) * 9) // 10], 4), "max": round(per_step[-1], 4)}
     dp_evidence = dist.evidence()          # every rank takes part (an all-reduce and an all-gather through the step's communicator)
 
-    # ---- per-kernel HIP-event timing on the launch stream (separate, un-timed steps)
+    # ---- --full: per-kernel HIP-event timing on the launch stream (separate, un-timed steps)
     roof = None
     kern = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         ops.prof_reset()
         ops.prof_enable(True)
         nprof = 2
@@ -457,7 +507,7 @@ def main():
                    for n, ms, fl, by, _, us in recs[:len(recs) // 2]]
             with open(args.kernels_out, "w") as f:
                 json.dump({"ms_per_step_sum": round(sum(k[1] for k in kern.values()) / 2, 4), "kernels": table, "sequence": seq}, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.arch, args.cpu_sample_batch or B, args.sigma)
         print(json.dumps(out), flush=True)
     dist.barrier()

@@ -89,3 +89,25 @@ def test_committed_traffic_profile_matches_the_kernel_sources():
 def test_bench_cli_parses_without_a_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--strong" in out.stdout and "blur256" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones_at_fixed_positions(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files; an array above DUMP_MAX_ELEMS becomes a sample at positions that depend on its
+    size only, so that two runs (two builds) write comparable files."""
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 1000
+    big = torch.arange(n, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("metrics", [0.0, 1.5, -2.25]), ("w", torch.arange(10, dtype=torch.int32)), ("big", big),
+                                               ("empty", torch.zeros(0))])
+    m = np.load(tmp_path / "a" / "metrics.npy")
+    assert m.dtype == np.float64 and m.tolist() == [0.0, 1.5, -2.25]
+    w = np.load(tmp_path / "a" / "w.npy")
+    assert w.dtype == np.float32 and w.tolist() == list(range(10))
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_MAX_ELEMS and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[-1] < n                     # sorted distinct positions of the original array
+    assert not (tmp_path / "a" / "empty.npy").exists()

@@ -243,7 +243,7 @@ def test_checkpoint_manager_ignores_and_removes_temp_files_of_a_crashed_save(tmp
         not [n for n in os.listdir(tmp_path / "c") if n.endswith(".tmp.npz")]
 
 
-def test_feed_images_to_metric_callback_counts():
+def test_feed_images_to_metric_callback_counts(tmp_path):
     class M:
         name = "m"
         def __init__(self): self.n = 0
@@ -257,7 +257,7 @@ def test_feed_images_to_metric_callback_counts():
     model = Model()
     model.images = (torch.zeros(32, 2), torch.zeros(32, 2))
     model.n_img = 0
-    model.summary_writer = _SummaryWriter("/tmp/bg_cb_logs")
+    model.summary_writer = _SummaryWriter(str(tmp_path / "logs"))
     cb = callbacks.FeedImagesToMetricCallback(M(), lambda x: x, num_samples=50, every_n_examples=100)
     cb.set_model(model)
     for b in range(8):

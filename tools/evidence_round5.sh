@@ -25,6 +25,6 @@ for m in replay eager; do
   rm -rf $OUT/trace_mnist_$m
 done
 for route in torch abi; do
-  BGAN_DP_COLLECTIVE=$route BGAN_DP_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 1 --no-cpu-baseline 2>$OUT/dp1_$route.err | tail -1 > $OUT/${tag}_bench_dp1_$route.json; cut -c1-120 $OUT/${tag}_bench_dp1_$route.json
+  BGAN_DP_COLLECTIVE=$route BGAN_DP_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 1 --no-cpu-baseline 2>$OUT/dp1_$route.err | tail -1 > $OUT/${tag}_bench_dp1_$route.json; cut -c1-120 $OUT/${tag}_bench_dp1_$route.json
 done
 echo done

@@ -10,7 +10,7 @@ tag=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=${OUT:-$root/gpurun_out}
 for d in stats fetch write; do if [ -e $out/pmc_${tag}_$d ]; then echo "$out/pmc_${tag}_$d exists: pick a new tag" >&2; exit 2; fi; done
-common="--steps 5 --warmup 2 --no-cpu-baseline"
+common="--full --steps 5 --warmup 2 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/pmc_${tag}_stats -- python3 $root/bench.py $common --kernels-out $out/pmc_${tag}_kernels.json "$@" > $out/pmc_${tag}_bench.json 2> $out/pmc_${tag}_stats.log
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_${tag}_fetch -- python3 $root/bench.py $common "$@" > /dev/null 2> $out/pmc_${tag}_fetch.log
 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $out/pmc_${tag}_write -- python3 $root/bench.py $common "$@" > /dev/null 2> $out/pmc_${tag}_write.log
