@@ -48,6 +48,9 @@ SIGNATURES = {
     "bg_conv2d_splitk_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "bg_conv2d_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _p]),
     "bg_conv2d_bwd_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _p]),
+    "bg_conv2d_fwd_math": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _p, _i]),
+    "bg_conv2d_bwd_data_math": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _p, _i]),
+    "bg_conv2d_math_taken": (_i, [_i] * 9),
     "bg_conv2d_bwd_filter_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i, _i]),
     "bg_conv2d_bwd_filter": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _z, _p]),
     "bg_transpose_last2": (_i, [_p, _p, _i, _i, _i, _p]),

@@ -172,6 +172,7 @@ class Net:
         self._taps_cache = {}
         self._splitk_bytes = {}
         self.rng_offset = 0
+        self.conv_math = "fp32"   # conv forward / data-gradient math of every call site below (ops.CONV_MATH; WGAN(conv_math=...))
         self.sync_bn = True       # data parallel: BatchNormalization statistics over the global batch
         # statistics in the producing conv's epilogue: opt-in since round 3 -- the plain gather-GEMM variant now stores float4
         # (transposed accumulators), the statistics variant cannot, and the separate statistics pass costs less than that (C2
@@ -377,9 +378,9 @@ class Net:
                 else:
                     epi = self._epi(*geom, EPI_NONE, bias=bias)
                 if st.kind == "conv":
-                    ops.conv2d_fwd(xin, self.store.transposed_kernel(st.lin), tgt, st.lin.k, st.lin.stride, epi)
+                    ops.conv2d_fwd(xin, self.store.transposed_kernel(st.lin), tgt, st.lin.k, st.lin.stride, epi, math=self.conv_math)
                 else:   # Conv2DTranspose forward == data-gradient of the conv with the same kernel array
-                    ops.conv2d_bwd_data(xin, st.lin.vars["kernel"], tgt, st.lin.k, st.lin.stride, epi)
+                    ops.conv2d_bwd_data(xin, st.lin.vars["kernel"], tgt, st.lin.k, st.lin.stride, epi, math=self.conv_math)
                 stat_rows = ops.conv2d_stats_rows(epi) if st.bn is not None else 0
             if st.bn is not None and not (st.kind != "dense" and not training and bias is None):
                 C = st.out_shape[-1]
@@ -566,9 +567,9 @@ class Net:
                 K, N = st.in_shape[0], st.out_shape[0]
                 ops.gemm(dzx, lin.vars["kernel"], tgt, Bx, K, N, transB=True)
             elif st.kind == "conv":
-                ops.conv2d_bwd_data(dzx, lin.vars["kernel"], tgt, lin.k, lin.stride, epi)
+                ops.conv2d_bwd_data(dzx, lin.vars["kernel"], tgt, lin.k, lin.stride, epi, math=self.conv_math)
             else:
-                ops.conv2d_fwd(dzx, self.store.transposed_kernel(lin), tgt, lin.k, lin.stride, epi)
+                ops.conv2d_fwd(dzx, self.store.transposed_kernel(lin), tgt, lin.k, lin.stride, epi, math=self.conv_math)
             if overlap:
                 Cp = prev.out_shape[-1]
                 gp = tgt.view(B, *prev.out_shape)
@@ -623,7 +624,7 @@ class Net:
                 if self.capture_branches is not None:            # test instrumentation: the signs about to be overwritten
                     self.capture_branches.append((ah > 0).cpu().numpy())
                 epi = self._epi(False, Bh, H, W, Ci, lin.filters, lin.k, lin.stride, EPI_MUL_GRAD, ref=ah, alpha=st.alpha)
-                ops.conv2d_fwd(xin[lo:hi], self.store.transposed_kernel(lin), ah, lin.k, lin.stride, epi)   # in place: ref == out
+                ops.conv2d_fwd(xin[lo:hi], self.store.transposed_kernel(lin), ah, lin.k, lin.stride, epi, math=self.conv_math)   # in place: ref == out
             elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
                 K = st.in_shape[0]
                 ws = self.workspace(ops.colsum_workspace_bytes(Bh, K))
@@ -655,7 +656,7 @@ class Net:
                 epi = self._epi(False, Bc, H, W, Ci, lin.filters, lin.k, lin.stride, EPI_MUL_GRAD, ref=ctx.a[i], alpha=st.alpha)
                 if reducer is not None:     # this layer's gradient (first-order pass + this wgrad) is complete
                     reducer.ready(*st_.train_range(lin, st.bn))
-                ops.conv2d_fwd(vin, self.store.transposed_kernel(lin), vo, lin.k, lin.stride, epi)
+                ops.conv2d_fwd(vin, self.store.transposed_kernel(lin), vo, lin.k, lin.stride, epi, math=self.conv_math)
                 v = vo
             elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
                 K = st.in_shape[0]

@@ -377,11 +377,15 @@ class Sequential(Layer):
         self.build()
         return self._store
 
+    # conv forward / data-gradient math of this model's engine (ops.CONV_MATH); WGAN(conv_math=...) sets it on both models
+    conv_math = "fp32"
+
     def net(self):
         from .engine import Net
         if self._net is None:
             self.build()
             self._net = Net(self.flat_layers(), self._store)
+        self._net.conv_math = self.conv_math
         return self._net
 
     # ---- Keras surface

@@ -129,27 +129,55 @@ def blur3_lerp(f, r, alpha_b, y3, taps_d, n_taps):
 
 
 # ------------------------------------------------------------------ conv family
-def conv2d_fwd(x, wT, y, ksize, stride, epi=None):
+# conv math modes of the forward / data gradient (include/bgan.h bg_conv_math): "fp32" is the plain entry point, exactly;
+# "bf16x6" the opt-in split-bf16 kernel on the geometries of its dispatch table (the rest of such a call runs fp32)
+CONV_MATH = {"fp32": 0, "bf16x6": 1}
+
+
+def conv_math_code(math):
+    """The bg_conv_math code of a mode name; ValueError for anything else."""
+    if not isinstance(math, str) or math not in CONV_MATH:
+        raise ValueError(f"conv math {math!r}: expected one of {sorted(CONV_MATH)}")
+    return CONV_MATH[math]
+
+
+def conv2d_math_taken(bwd_data, B, H, W, Cin, Cout, ksize, stride, math):
+    """True when a call of that geometry in mode ``math`` runs the split-bf16 kernel (bg_conv2d_math_taken)."""
+    return bool(_lib.load().bg_conv2d_math_taken(int(bwd_data), B, H, W, Cin, Cout, ksize, stride, conv_math_code(math)))
+
+
+def conv2d_fwd(x, wT, y, ksize, stride, epi=None, math="fp32"):
     """x [B,H,W,Cin], wT [k*k,Cout,Cin] -> y [B,Ho,Wo,Cout]."""
+    code = conv_math_code(math)
     _f32(x, wT, y)
     B, H, W, Cin = x.shape
     Cout = y.shape[3]
     assert wT.numel() == ksize * ksize * Cin * Cout, (wT.shape, Cin, Cout)
     assert tuple(y.shape) == (B, same_out(H, stride), same_out(W, stride), Cout), (x.shape, y.shape)
-    check(_lib.load().bg_conv2d_fwd(_ptr(x), _ptr(wT), _ptr(y), B, H, W, Cin, Cout, ksize, stride,
-                                    C.byref(epi) if epi is not None else None, _stream()), "bg_conv2d_fwd")
+    e = C.byref(epi) if epi is not None else None
+    if code == 0:
+        check(_lib.load().bg_conv2d_fwd(_ptr(x), _ptr(wT), _ptr(y), B, H, W, Cin, Cout, ksize, stride, e, _stream()), "bg_conv2d_fwd")
+    else:
+        check(_lib.load().bg_conv2d_fwd_math(_ptr(x), _ptr(wT), _ptr(y), B, H, W, Cin, Cout, ksize, stride, e, _stream(), code),
+              "bg_conv2d_fwd_math")
     return y
 
 
-def conv2d_bwd_data(dy, w, dx, ksize, stride, epi=None):
+def conv2d_bwd_data(dy, w, dx, ksize, stride, epi=None, math="fp32"):
     """dy [B,Ho,Wo,Cout], w [k*k,Cin,Cout] -> dx [B,H,W,Cin]."""
+    code = conv_math_code(math)
     _f32(dy, w, dx)
     B, H, W, Cin = dx.shape
     Cout = dy.shape[3]
     assert w.numel() == ksize * ksize * Cin * Cout
     assert tuple(dy.shape) == (B, same_out(H, stride), same_out(W, stride), Cout), (dy.shape, dx.shape)
-    check(_lib.load().bg_conv2d_bwd_data(_ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, ksize, stride,
-                                         C.byref(epi) if epi is not None else None, _stream()), "bg_conv2d_bwd_data")
+    e = C.byref(epi) if epi is not None else None
+    if code == 0:
+        check(_lib.load().bg_conv2d_bwd_data(_ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, ksize, stride, e, _stream()),
+              "bg_conv2d_bwd_data")
+    else:
+        check(_lib.load().bg_conv2d_bwd_data_math(_ptr(dy), _ptr(w), _ptr(dx), B, H, W, Cin, Cout, ksize, stride, e, _stream(), code),
+              "bg_conv2d_bwd_data_math")
     return dx
 
 

@@ -128,7 +128,8 @@ class WGAN:
                  config: TrainingConfig, *args, reproduce_vector_loss_quirk: bool = True, sync_metrics: bool = True,
                  sync_batchnorm: bool = True, merge_critic_passes: bool = True, gp_zero_norm_guard: bool = False,
                  merge_gp_filter_gradients: bool = True, step_replay: bool = True, persistent_input: bool = False,
-                 **kwargs):
+                 conv_math: str = "fp32", **kwargs):
+        ops.conv_math_code(conv_math)        # ValueError before anything is built
         self.hparams = hyperparams
         if dist.world_size() > 1 and int(hyperparams.global_batch_size) != int(hyperparams.batch_size) * dist.world_size():
             import warnings
@@ -187,6 +188,21 @@ class WGAN:
         self._rng_off = 0
         self._bufs = {}
         self._injected = None
+        self.conv_math = conv_math
+
+    @property
+    def conv_math(self):
+        """Math of the conv forward / data-gradient launches of the training step and generate_samples: "fp32" (default, the
+        plain kernels) or "bf16x6" (opt-in split-bf16 kernel on the geometries of its dispatch table, include/bgan.h
+        BG_CONV_MATH_BF16X6).  Filter gradients, dense GEMMs, BatchNorm, blur and Adam stay fp32 in either mode."""
+        return self._conv_math
+
+    @conv_math.setter
+    def conv_math(self, value):
+        ops.conv_math_code(value)
+        self._conv_math = value
+        self.generator.conv_math = value
+        self.discriminator.conv_math = value
 
     # ------------------------------------------------------------------ small helpers
     @property
@@ -310,7 +326,7 @@ class WGAN:
         return (kind, tuple(reals.shape), reals.data_ptr(), D.blur_n_taps(), G.store.tr_dirty, D.store.tr_dirty, self.merge_critic_passes,
                 self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
                 self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
-                G.store.n_train, D.store.n_train, G.bn_bwd_read_y, _env_switches(), hp)
+                G.store.n_train, D.store.n_train, G.bn_bwd_read_y, G.conv_math, D.conv_math, _env_switches(), hp)
 
     def _exit_state(self):
         G, D = self.generator.net(), self.discriminator.net()

@@ -69,6 +69,8 @@ def main(argv=None):
     parser.add_argument("--epochs", type=int, default=10)
     parser.add_argument("--max_batches", type=int, default=None)
     parser.add_argument("--results_dir", default="results")
+    parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
+                        help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
     args = parser.parse_args(argv)
     hyperparameters = BlurredWGANGP.HyperParameters.from_args(args)
     config = TrainingConfig.from_args(args)
@@ -83,7 +85,7 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
     gen, disc = DCGANGenerator(), DCGANDiscriminator()
-    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config)
+    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math)
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)

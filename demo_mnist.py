@@ -76,6 +76,8 @@ def main(argv=None):
     parser.add_argument("--epochs", type=int, default=10)
     parser.add_argument("--max_batches", type=int, default=None, help="truncate the epoch (smoke runs)")
     parser.add_argument("--results_dir", default="results")
+    parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
+                        help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
     args = parser.parse_args(argv)
     hyperparameters = BlurredWGANGP.HyperParameters.from_args(args)
     config = TrainingConfig.from_args(args)
@@ -96,7 +98,7 @@ def main(argv=None):
 
     gen = DCGANGenerator()
     disc = DCGANDiscriminator()
-    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config)
+    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math)
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)

@@ -148,6 +148,26 @@ int bg_conv2d_fwd(const float* x, const float* wT_d, float* y, int B, int H, int
 /* dx[B,H,W,Cin] = conv^T(dy[B,Ho,Wo,Cout], w) ; w_d = [k*k][Cin][Cout] (TF Conv2D layout) */
 int bg_conv2d_bwd_data(const float* dy, const float* w_d, float* dx, int B, int H, int W, int Cin, int Cout,
                        int ksize, int stride, const bg_epilogue* epi, void* stream);
+/* Conv math modes of the forward and data gradient (bg_conv2d_fwd_math / bg_conv2d_bwd_data_math).
+ *   BG_CONV_MATH_FP32    exactly bg_conv2d_fwd / bg_conv2d_bwd_data: fp32 operands on the fp32 matrix pipe.
+ *   BG_CONV_MATH_BF16X6  opt-in split-bf16 math: every fp32 operand element is split exactly into three bf16 pieces
+ *                        (hi = top 16 bits, mid = top 16 bits of x - hi, lo = round-to-nearest of the rest) and a product is
+ *                        rebuilt from the six cross terms hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid on the bf16 matrix pipe,
+ *                        accumulated in fp32.  Accuracy contract: the terms left out are below 2^-24 of each product, so the
+ *                        error against an exact result is of the order of the fp32 path's (fp32 accumulation order dominates
+ *                        both) and within the same bounds; results are NOT bit-identical to BG_CONV_MATH_FP32, but are
+ *                        bit-reproducible from run to run (fixed summation order, no atomics).  Inf / NaN inputs give the same
+ *                        Inf / NaN outputs as the fp32 path.  Only the geometries of a static table (measured faster) run the
+ *                        split kernel -- bg_conv2d_math_taken says which; every other call, and every call whose epilogue or
+ *                        statistics buffer the split kernel does not take, runs the fp32 path unchanged. */
+typedef enum { BG_CONV_MATH_FP32 = 0, BG_CONV_MATH_BF16X6 = 1 } bg_conv_math;
+/* the same calls with a math mode; BG_ERR_UNSUPPORTED for an unknown mode */
+int bg_conv2d_fwd_math(const float* x, const float* wT_d, float* y, int B, int H, int W, int Cin, int Cout,
+                       int ksize, int stride, const bg_epilogue* epi, void* stream, int math);
+int bg_conv2d_bwd_data_math(const float* dy, const float* w_d, float* dx, int B, int H, int W, int Cin, int Cout,
+                            int ksize, int stride, const bg_epilogue* epi, void* stream, int math);
+/* pure host query: 1 when the call of that geometry in mode `math` runs the split-bf16 kernel (0 for BG_CONV_MATH_FP32) */
+int bg_conv2d_math_taken(int bwd_data, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int math);
 /* dw[k,k,Cin,Cout] = beta*dw + scale * sum_pixels x (x) dy.  ws_d: bg_conv2d_bwd_filter_workspace_bytes */
 size_t bg_conv2d_bwd_filter_workspace_bytes(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
 int bg_conv2d_bwd_filter(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Cout,
