@@ -87,6 +87,9 @@ SIGNATURES = {
     "bg_wgan_g_loss": (_i, [_p, _i, _f, _p, _p, _p]),
     "bg_u8_normalize_resize_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bg_adam_f32": (_i, [_p, _p, _p, _p, _z, _f, _f, _f, _f, _p]),
+    "bg_sgd_f32": (_i, [_p, _p, _p, _z, _f, _f, _i, _p]),
+    "bg_rmsprop_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _i, _p]),
+    "bg_adam_amsgrad_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _p]),
     "bg_uniform_f32": (_i, [_p, _z, _u64, _u64, _p]),
     "bg_keep_mask_u8": (_i, [_p, _z, _f, _u64, _u64, _p]),
     "bg_program_create": (_i, [C.POINTER(_p), _i]),
@@ -111,7 +114,7 @@ SIGNATURES = {
 }
 
 COMM_ID_BYTES = 128
-BIND_ADAM_LR, BIND_RNG_OFFSET = 1, 2      # include/bgan.h BG_BIND_*
+BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR = 1, 2, 3      # include/bgan.h BG_BIND_*
 
 _lib = None
 

@@ -25,6 +25,9 @@ class ExponentialDecay:
     def __init__(self, initial_learning_rate, decay_steps, decay_rate, staircase=False):
         self.initial, self.decay_steps, self.rate, self.staircase = float(initial_learning_rate), float(decay_steps), float(decay_rate), staircase
 
+    def get_config(self):
+        return {"initial_learning_rate": self.initial, "decay_steps": self.decay_steps, "decay_rate": self.rate, "staircase": self.staircase}
+
     def __call__(self, step):
         p = np.float32(float(step)) / np.float32(self.decay_steps)
         if self.staircase:

@@ -1,7 +1,10 @@
 """Checkpoint / resume: stands in for ``tf.train.Checkpoint(gan=gan)`` + ``CheckpointManager``
 (demo_mnist.py:145-163, callbacks.py:239-246).  One ``.npz`` per checkpoint holding both networks' variables
-(weights + BN moving statistics), both Adams' slots and step counts, ``n_img``, ``n_batches``, ``blur.std`` and the
-positions of the step's random streams (latents / alpha / dropout), so a resumed run continues the uninterrupted one.
+(weights + BN moving statistics), both optimizers (class, ``get_config()`` as JSON, learning rate, step count and every slot
+buffer in use), ``n_img``, ``n_batches``, ``blur.std`` and the positions of the step's random streams (latents / alpha /
+dropout), so a resumed run continues the uninterrupted one.  A checkpoint restores only into a model whose optimizers have the
+same class and static configuration (``ValueError`` otherwise); one written before optimizers were recorded (``m`` / ``v``
+only) is a default Adam's.
 
 Like ``tf.train.CheckpointManager`` the manager orders checkpoints by SAVE ORDER, not by the number in the file name
 (``SaveModelCallback`` numbers files with a counter that restarts at every ``fit``, callbacks.py:245): the order lives in
@@ -15,7 +18,15 @@ import re
 import numpy as np
 import torch
 
+from . import optimizers
+
 INDEX = "checkpoint"
+
+_LEGACY_OPT = ("Adam", optimizers.Adam().static_config())       # checkpoints without an optimizer record
+
+
+def _json_default(x):
+    return repr(x)
 
 
 _CKPT_NAME = re.compile(r"^ckpt-\d+\.npz$")
@@ -68,13 +79,19 @@ class CheckpointManager:
         if hasattr(g, "blur"):
             d["std"] = np.float32(float(g.std))
         for tag, model in (("g", g.generator), ("d", g.discriminator)):
-            st = model.store
-            st.ensure_opt_state()
+            st, opt = model.store, optimizers.get_optimizer(model)
+            opt.attach(st)
             d[f"{tag}_theta"] = st.theta.cpu().numpy()
             d[f"{tag}_state"] = st.state.cpu().numpy()
             d[f"{tag}_m"] = st.m.cpu().numpy()
             d[f"{tag}_v"] = st.v.cpu().numpy()
-            d[f"{tag}_iterations"] = np.int64(model.optimizer.iterations)
+            if st.s3 is not None:
+                d[f"{tag}_s3"] = st.s3.cpu().numpy()
+            d[f"{tag}_iterations"] = np.int64(opt.iterations)
+            d[f"{tag}_opt_class"] = np.str_(type(opt).__name__)
+            d[f"{tag}_opt_config"] = np.str_(json.dumps(opt.get_config(), default=_json_default))
+            lr = opt.learning_rate
+            d[f"{tag}_opt_lr"] = np.float64(lr if not callable(lr) else np.nan)      # a schedule lives in the config
             d[f"{tag}_rng_offset"] = np.int64(int(model.net().rng_offset))        # dropout-mask stream of this network
         return d
 
@@ -114,11 +131,26 @@ class CheckpointManager:
         if "std" in d.files and hasattr(g, "blur"):
             g.std.assign(float(d["std"]))
         for tag, model in (("g", g.generator), ("d", g.discriminator)):
-            st = model.store
-            st.ensure_opt_state()
-            for name, buf in (("theta", st.theta), ("state", st.state), ("m", st.m), ("v", st.v)):
+            st, opt = model.store, optimizers.get_optimizer(model)
+            if f"{tag}_opt_class" in d.files:
+                saved = (str(d[f"{tag}_opt_class"]), json.loads(str(d[f"{tag}_opt_config"])))
+                saved_static = tuple(sorted((k, v) for k, v in saved[1].items() if k in dict(opt.static_config())))
+            else:
+                saved = saved_static = None
+            if (saved[0] if saved else _LEGACY_OPT[0]) != type(opt).__name__ or \
+                    (saved_static if saved else _LEGACY_OPT[1]) != opt.static_config():
+                what = f"{saved[0]}({saved[1]})" if saved else "Adam() (a checkpoint without an optimizer record)"
+                raise ValueError(f"{path}: the {'generator' if tag == 'g' else 'discriminator'} was saved with {what}, the model's "
+                                 f"optimizer is {opt!r}: the class and static configuration must match")
+            opt.attach(st)
+            if st.s3 is not None and f"{tag}_s3" not in d.files:
+                raise ValueError(f"{path}: no third slot saved for the {tag} optimizer {opt!r}")
+            bufs = [("theta", st.theta), ("state", st.state), ("m", st.m), ("v", st.v)] + ([("s3", st.s3)] if st.s3 is not None else [])
+            for name, buf in bufs:
                 buf.copy_(torch.from_numpy(d[f"{tag}_{name}"]))
-            model.optimizer.iterations = int(d[f"{tag}_iterations"])
+            opt.iterations = int(d[f"{tag}_iterations"])
+            if f"{tag}_opt_lr" in d.files and not callable(opt.learning_rate) and np.isfinite(d[f"{tag}_opt_lr"]):
+                opt.learning_rate = float(d[f"{tag}_opt_lr"])
             if f"{tag}_rng_offset" in d.files:
                 model.net().rng_offset = int(d[f"{tag}_rng_offset"])
             st.tr_dirty = True

@@ -208,6 +208,8 @@ class ParamStore:
         self.theta = torch.zeros(max(off_t, 1), dtype=torch.float32, device=self.device)
         self.state = torch.zeros(max(off_s, 1), dtype=torch.float32, device=self.device)
         self.grad = self.m = self.v = None
+        self.s3 = None              # third optimiser slot (optimizers.py: Adam's vhat, RMSprop's mg), allocated when a variant needs it
+        self.slot_owner = None      # the optimizer whose slots m / v / s3 are (optimizers.Optimizer.attach)
         self.step_count = 0
         for (layer, name, off, shape, trainable), val in zip(self.entries, init_vals):
             buf = self.theta if trainable else self.state

@@ -346,7 +346,7 @@ def bn_param_grads(sums, Cc, scale, dgamma, dbeta):
     check(_lib.load().bg_bn_param_grads_f32(_ptr(sums), Cc, scale, _ptr(dgamma), _ptr(dbeta), _stream()), "bg_bn_param_grads_f32")
 
 
-# ------------------------------------------------------------------ pointwise / losses / adam / rng
+# ------------------------------------------------------------------ pointwise / losses / optimisers / rng
 def lerp(r, f, alpha_b, out):
     B = r.shape[0]
     n_per = r.numel() // B
@@ -426,6 +426,25 @@ def u8_normalize_resize(src_u8, dst):
 def adam(theta, m, v, g, lr_t, b1=0.9, b2=0.999, eps=1e-7):
     assert theta.numel() == m.numel() == v.numel() == g.numel()
     check(_lib.load().bg_adam_f32(_ptr(theta), _ptr(m), _ptr(v), _ptr(g), theta.numel(), lr_t, b1, b2, eps, _stream()), "bg_adam_f32")
+
+
+def sgd(theta, a, g, lr, momentum=0.0, nesterov=False):
+    """tf.keras.optimizers.SGD's update; ``a`` (the momentum slot) may be None when momentum == 0."""
+    assert theta.numel() == g.numel() and (a is None or a.numel() == theta.numel())
+    check(_lib.load().bg_sgd_f32(_ptr(theta), _ptr(a), _ptr(g), theta.numel(), lr, momentum, int(bool(nesterov)), _stream()), "bg_sgd_f32")
+
+
+def rmsprop(theta, r, p, mg, g, lr, rho=0.9, momentum=0.0, eps=1e-7, centered=False):
+    """tf.keras.optimizers.RMSprop's update; ``p`` (momentum) / ``mg`` (centered) may be None when unused."""
+    assert theta.numel() == r.numel() == g.numel() and all(x is None or x.numel() == theta.numel() for x in (p, mg))
+    check(_lib.load().bg_rmsprop_f32(_ptr(theta), _ptr(r), _ptr(p), _ptr(mg), _ptr(g), theta.numel(), lr, rho, momentum, eps,
+                                     int(bool(centered)), _stream()), "bg_rmsprop_f32")
+
+
+def adam_amsgrad(theta, m, v, vhat, g, lr_t, b1=0.9, b2=0.999, eps=1e-7):
+    assert theta.numel() == m.numel() == v.numel() == vhat.numel() == g.numel()
+    check(_lib.load().bg_adam_amsgrad_f32(_ptr(theta), _ptr(m), _ptr(v), _ptr(vhat), _ptr(g), theta.numel(), lr_t, b1, b2, eps, _stream()),
+          "bg_adam_amsgrad_f32")
 
 
 def _draw_offset(out, offset, counter):

@@ -6,7 +6,7 @@ wgan.py:86-114,132-172, happens ONCE per program here).
   first call with a key    -> ``fn()`` eagerly (contexts, workspaces and optimiser slots get allocated);
   second call              -> ``fn()`` eagerly again, but every launch is also recorded (``Recorder``);
   every later call         -> the recorded program is replayed: the per-step scalars are written into the program's slots
-                              (Adam's lr_t, the RNG counter offsets -- the host counters advance exactly as the eager path
+                              (the optimisers' learning rates, the RNG counter offsets -- the host counters advance exactly as the eager path
                               advances them, so eager and replayed steps can be mixed freely and stay bit-identical), then ONE
                               ctypes call issues every kernel.  Data-parallel collectives are host actions: the replay is
                               split at the node indices where they were issued while recording.
@@ -15,7 +15,6 @@ arguments, dirty flags of the transposed weight copies); a new key is a new prog
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 import threading
 import warnings
@@ -123,16 +122,16 @@ class Recorder:
             setattr(obj, attr, v + inc)
         self.updates.append(update)
 
-    def bind_adam(self, opt, b1, b2):
-        """The next bg_adam_f32 launch takes lr_t of ``opt``'s next iteration."""
+    def bind_scalar(self, what, advance):
+        """The next optimiser launch (BIND_ADAM_LR: bg_adam_f32's lr_t; BIND_OPT_LR: bg_sgd_f32 / bg_rmsprop_f32's lr,
+        bg_adam_amsgrad_f32's lr_t) takes ``advance()``, the optimiser's scalar of its next iteration (which advances its
+        ``iterations``): a learning rate changed between steps, a schedule or a decay takes effect under replay."""
         s = self._slot()
-        _lib.check(self.lib.bg_program_bind_next(_lib.BIND_ADAM_LR, s), "bg_program_bind_next")
+        _lib.check(self.lib.bg_program_bind_next(what, s), "bg_program_bind_next")
         f64 = self.f64
 
         def update():
-            opt.iterations += 1
-            t = opt.iterations
-            f64[s] = float(opt.learning_rate) * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+            f64[s] = advance()
         self.updates.append(update)
 
     def host_action(self, fn):

@@ -6,7 +6,6 @@ Step order, training flags and loss algebra follow wgan.py:86-172, 234-285 inclu
 """
 from __future__ import annotations
 
-import math
 import numbers
 import os
 from contextlib import contextmanager
@@ -16,13 +15,10 @@ from typing import List
 import numpy as np
 import torch
 
-from . import dist, ops, program
+from . import dist, ops, optimizers, program
 from .gaussian_blur import Variable
 from .layers import Sequential, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
-
-ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7       # tf.keras.optimizers.Adam defaults (wgan.py:56)
-
 
 _KEY_ENV = ("BGAN_NO_FUSED_BLUR3", "BGAN_NO_FOLD_MANY", "BGAN_NO_FUSED_BN_STATS", "BG_BLUR_NO_ROWS", "BG_BLUR_NO_PANEL", "BG_BLUR_PANEL16", "BG_WGRAD_NO_STRIP")
 
@@ -70,24 +66,6 @@ class Mean:
 
     def result(self):
         return self.total / self.count if self.count else 0.0
-
-
-class _Adam:
-    """Keras Adam bookkeeping; the update itself is one fused launch over the model's flat buffer."""
-
-    def __init__(self, learning_rate=0.001):
-        self.learning_rate = learning_rate
-        self.iterations = 0
-
-    def apply(self, store):
-        self.iterations += 1
-        t = self.iterations
-        lr_t = float(self.learning_rate) * math.sqrt(1.0 - ADAM_B2 ** t) / (1.0 - ADAM_B1 ** t)
-        if program.active() is not None:        # step program: the recorded launch takes lr_t of the NEXT iteration from a slot
-            program.active().bind_adam(self, ADAM_B1, ADAM_B2)
-        ops.adam(store.theta[:store.n_train], store.m[:store.n_train], store.v[:store.n_train],
-                 store.grad[:store.n_train], lr_t, ADAM_B1, ADAM_B2, ADAM_EPS)
-        store.tr_dirty = True
 
 
 class _SummaryWriter:
@@ -139,13 +117,16 @@ class WGAN:
                           f"{hyperparams.batch_size}: the Wasserstein / penalty gradient ratio differs from the single-device "
                           "step at the global batch (set global_batch_size = batch_size * replicas)")
         if str(self.hparams.optimizer).lower() != "adam":
-            raise NotImplementedError("only the reference's default optimizer 'adam' is implemented (wgan.py:43,56)")
+            raise NotImplementedError("of the optimizer names only the reference's default 'adam' is implemented (wgan.py:43,56); "
+                                      "other optimizers are objects assigned after construction, e.g. "
+                                      "gan.discriminator.optimizer = blurred_gan_amd.optimizers.RMSprop(5e-5)")
+        # Keras optimizer objects (optimizers.py); any supported one may be assigned to either network at any time
         self.generator = generator
         self.generator.build()
-        self.generator.optimizer = _Adam(self.hparams.learning_rate)
+        self.generator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.discriminator = discriminator
         self.discriminator.build()
-        self.discriminator.optimizer = _Adam(self.hparams.learning_rate)
+        self.discriminator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.d_steps_per_g_step = self.hparams.d_steps_per_g_step
         self.batch_size = None
         self.config = config
@@ -255,6 +236,9 @@ class WGAN:
         self.batch_size = int(reals.shape[0])
         self._injected = randomness
         self._defer_metrics = True
+        for model in (self.generator, self.discriminator):
+            # the optimizers' slot buffers are in place before the step keys read their addresses
+            optimizers.get_optimizer(model).attach(model.store)
         replay = self.step_replay and randomness is None and self._replayable()
         try:
             if replay:
@@ -326,7 +310,15 @@ class WGAN:
         return (kind, tuple(reals.shape), reals.data_ptr(), D.blur_n_taps(), G.store.tr_dirty, D.store.tr_dirty, self.merge_critic_passes,
                 self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
                 self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
-                G.store.n_train, D.store.n_train, G.bn_bwd_read_y, G.conv_math, D.conv_math, _env_switches(), hp)
+                G.store.n_train, D.store.n_train, G.bn_bwd_read_y, G.conv_math, D.conv_math, _env_switches(), hp,
+                self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
+
+    @staticmethod
+    def _optimizer_key(model):
+        """A network's optimizer as it shapes the launch list: class, static configuration (variant, constants baked into the
+        launch) and the addresses of its slot buffers (a program recorded on another optimizer's slots must never replay)."""
+        opt, st = model.optimizer, model.store
+        return (type(opt).__name__, opt.static_config(), *(0 if b is None else b.data_ptr() for b in (st.m, st.v, st.s3)))
 
     def _exit_state(self):
         G, D = self.generator.net(), self.discriminator.net()
@@ -462,7 +454,7 @@ class WGAN:
                 v0 = D.apply_blur(gbar, self._buf("v0", tuple(g.shape))) if D.blur is not None else gbar
                 D.gp_second_order(chat, v0, reducer=red)
         red.finish()
-        self.discriminator.optimizer.apply(store)
+        optimizers.get_optimizer(self.discriminator).apply(store)
         disc_loss = None              # inside train_on_batch the value is read with the rest of the step's metrics
         if self.sync_metrics and not self._defer_metrics:
             m = self._read_metrics()
@@ -519,7 +511,7 @@ class WGAN:
         red = dist.GradReducer(store.grad, store.n_train)
         G.backward(cg, dfakes, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=red)
         red.finish()
-        self.generator.optimizer.apply(store)
+        optimizers.get_optimizer(self.generator).apply(store)
         if self.sync_metrics and not self._defer_metrics:
             m = self._read_metrics()
             self._record_g_metrics(m[8:12])

@@ -292,6 +292,24 @@ int bg_u8_normalize_resize_f32(const uint8_t* src, float* dst, int B, int Hs, in
 int bg_adam_f32(float* theta, float* m, float* v, const float* g, size_t n, float lr_t, float b1, float b2,
                 float eps, void* stream);
 
+/* ---- optimisers: the Keras objects a user assigns to gan.<net>.optimizer (wgan.py:56-61,141,167; TF 2.5 optimizer_v2) --
+ * All three take a 16-byte aligned theta / slot / gradient (BG_ERR_BAD_ALIGNMENT otherwise) and any n (a scalar tail covers
+ * n % 4).  lr is the step's rate after the host applied the schedule and the inverse-time decay (Adam: lr_t with the bias
+ * correction); under a step program it is bound with BG_BIND_OPT_LR. */
+/* tf.keras.optimizers.SGD: ResourceApplyGradientDescent (momentum 0; a may be NULL) / ResourceApplyKerasMomentum
+ * (a = momentum*a - lr*g; theta += a, or theta += momentum*a - lr*g with nesterov) */
+int bg_sgd_f32(float* theta, float* a, const float* g, size_t n, float lr, float momentum, int nesterov, void* stream);
+/* tf.keras.optimizers.RMSprop: r = rho*r + (1-rho)*g^2 ; centered: mg = rho*mg + (1-rho)*g, d = r - mg^2 (else d = r);
+ * momentum 0 (Keras' Python path): theta -= lr*g / (sqrt(d) + eps) ; momentum > 0 (ResourceApplyRMSProp /
+ * ResourceApplyCenteredRMSProp): p = momentum*p + lr*g / sqrt(d + eps), theta -= p.  p may be NULL when momentum == 0, mg when
+ * centered == 0. */
+int bg_rmsprop_f32(float* theta, float* r, float* p, float* mg, const float* g, size_t n, float lr, float rho, float momentum,
+                   float eps, int centered, void* stream);
+/* tf.keras.optimizers.Adam(amsgrad=True): ResourceApplyAdamWithAmsgrad -- bg_adam_f32's m / v, vhat = max(vhat, v),
+ * theta -= lr_t*m / (sqrt(vhat) + eps).  Adam without amsgrad (any beta / epsilon) is bg_adam_f32. */
+int bg_adam_amsgrad_f32(float* theta, float* m, float* v, float* vhat, const float* g, size_t n, float lr_t, float b1, float b2,
+                        float eps, void* stream);
+
 /* ---- RNG: tf.random.uniform (wgan.py:118,237) and Dropout masks; counter-based, own stream ---- */
 int bg_uniform_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint64_t offset, void* stream);
@@ -304,9 +322,9 @@ int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint
  * While recording, every kernel launch of the calling thread is executed AND appended to `p` as (kernel, grid, block, LDS bytes,
  * a by-value copy of every kernel argument).  bg_program_replay(p, first, last, stream) issues nodes [first, last) (last < 0 =
  * all) on `stream` -- no geometry checks, tap tables, grid planning or host language in between.  What changes per step:
- *   - Adam's lr_t and the RNG counter offsets: announce bg_program_bind_next(what, slot) right before the call that owns the
- *     argument; the recorded launch then re-reads slots_f64[slot] (BG_BIND_ADAM_LR) / slots_u64[slot] (BG_BIND_RNG_OFFSET) before
- *     every replay.  The slot arrays belong to the program and are written directly by the host.
+ *   - the optimisers' learning rates and the RNG counter offsets: announce bg_program_bind_next(what, slot) right before the call
+ *     that owns the argument; the recorded launch then re-reads slots_f64[slot] (BG_BIND_ADAM_LR, BG_BIND_OPT_LR) /
+ *     slots_u64[slot] (BG_BIND_RNG_OFFSET) before every replay.  The slot arrays belong to the program and are written directly by the host.
  *   - the blur taps' VALUES live in a caller-owned device buffer the host refreshes in stream order; a changed tap COUNT selects
  *     other kernels and needs a newly recorded program (the host keeps one per count).
  *   - collectives (data parallel) are the host's: it splits the replay at the node indices bg_program_size() returned when the
@@ -325,6 +343,7 @@ int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint
 typedef struct bg_program bg_program;
 #define BG_BIND_ADAM_LR 1     /* bg_adam_f32: lr_t <- (float) slots_f64[slot]                         */
 #define BG_BIND_RNG_OFFSET 2  /* bg_uniform_f32, bg_keep_mask_u8: offset <- slots_u64[slot]            */
+#define BG_BIND_OPT_LR 3      /* bg_sgd_f32, bg_rmsprop_f32: lr, bg_adam_amsgrad_f32: lr_t <- (float) slots_f64[slot] */
 int bg_program_create(bg_program** out, int n_slots);
 int bg_program_destroy(bg_program* p);
 int bg_program_record_begin(bg_program* p);
