@@ -24,7 +24,8 @@ Rccl g_rccl;
 
 int bind_rccl() {
   if (g_rccl.handle) return BG_OK;
-  const char* names[] = {getenv("BGAN_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+  static const char* const env_lib = getenv("BGAN_RCCL_LIB");
+  const char* names[] = {env_lib, "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
   void* h = nullptr;
   for (const char* n : names) {
     if (!n || !*n) continue;

@@ -477,26 +477,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (BM == 64 && BN == 64 && !S
   const unsigned long long dg_t0 = __builtin_amdgcn_s_memtime(), dg_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
   const int nsteps2 = (nsteps + 1) & ~1;                       // steps come in (even, odd) pairs; a padded step adds zeros
-#if defined(IGEMM_PRIO_ROT) || defined(IGEMM_PRIO_INV)
-  // experiment (profiles/r05_a_gather_gemm_limits.md): the four workgroups of a CU do not share its matrix pipes evenly -- they end
-  // one after the other, and the CU's last quarter runs with one to three of them.  Wave priority by residency slot, fixed
-  // (youngest first) or rotating every eight steps.
-  const int prio_slot = (int)((((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) >> 8) & 3u);
-#endif
-#if defined(IGEMM_PRIO_INV)
-  switch (prio_slot) { case 0: __builtin_amdgcn_s_setprio(0); break; case 1: __builtin_amdgcn_s_setprio(1); break; case 2: __builtin_amdgcn_s_setprio(2); break; default: __builtin_amdgcn_s_setprio(3); break; }
-#endif
   for (int step = 0; step < nsteps2; step += 2) {
-#if defined(IGEMM_PRIO_ROT)
-    if ((step & 7) == 0) {
-      switch (((step >> 3) + prio_slot) & 3) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-      }
-    }
-#endif
     step_body(0, [&]() { lstore(1, regA1, regB1); gload(regA1, regB1); });
     if (--c_left == 0) phase_done();
     step_body(1, [&]() { lstore(0, regA0, regB0); gload(regA0, regB0); });
@@ -1240,9 +1221,8 @@ int plan_splitk(const GatherParams& p, int bm, int bn, int /*bk*/) {
   if (skipping && wgs >= min_wgs && wgs <= 2 * min_wgs && min_steps >= 64) {
     // round 3: the cost-sorted snake order balances the CUs of ONE round of resident workgroups, so the split only has to fill
     // that round (1024 slots), not make short workgroups: 768 tiles run unsplit (D4 forward of the merged critic pass
-    // 0.188 -> 0.159 ms), 1024 unsplit (G2 data gradient 0.185 -> 0.173), 512 in two halves as before.  BG_SPLITK_OLD=1: round-2 rule
-    static const int old_rule = getenv("BG_SPLITK_OLD") ? 1 : 0;
-    const int ks = old_rule ? (int)std::min<long>(4, 4L * min_wgs / wgs) : (int)std::max<long>(1, 2L * min_wgs / wgs);
+    // 0.188 -> 0.159 ms), 1024 unsplit (G2 data gradient 0.185 -> 0.173), 512 in two halves as before
+    const int ks = (int)std::max<long>(1, 2L * min_wgs / wgs);
     return std::max(1, std::min(ks, min_steps / 32));
   }
   if (wgs >= 2 * min_wgs || min_steps < 32) return 1;
@@ -1375,26 +1355,11 @@ int launch_igemm(GatherParams& p, const bg_epilogue* epi, void* stream, const ch
 
 template <int BK>
 int dispatch_igemm(GatherParams& p, const bg_epilogue* epi, void* stream, const char* tag) {
-  const int Mmax = max_phase_m(p);
-  // Pick the tile that keeps >= 2 workgroups per CU resident (two waves per SIMD: one issues MFMAs while the
-  // other runs its loader segment); bigger tiles only when the grid still fills the chip twice over.
-  auto wgs = [&](int bm, int bn) { return (long)bg::cdiv(Mmax, bm) * bg::cdiv(p.N, bn) * p.nphase; };
-  const long kFull = 2 * 256;
-  static const int force = getenv("BG_IGEMM_TILE") ? atoi(getenv("BG_IGEMM_TILE")) : 0;   // tuning aid: 1..4
-  int pick;
-  if (force) pick = force;
-  else if (p.N <= 32) pick = 3;
-  else if (wgs(64, 64) <= 4 * kFull || p.N < 128) pick = 4;      // measured: 64x64 at 4 WGs/CU beats the larger tiles
-  else pick = 4;
-  if (pick == 3 && p.N > 32) pick = 2;
-  switch (pick) {
-    case 1: return launch_igemm<128, 128, BK, 2, 2>(p, epi, stream, tag);
-    case 5: return launch_igemm<128, 128, BK, 2, 4>(p, epi, stream, tag);    // 8 waves, 64x32 per wave
-    case 6: return launch_igemm<128, 64, BK, 4, 2>(p, epi, stream, tag);     // 8 waves, 32x32 per wave
-    case 2: return launch_igemm<128, 64, BK, 2, 2>(p, epi, stream, tag);
-    case 3: return launch_igemm<128, 32, BK, 4, 1>(p, epi, stream, tag);
-    default: return launch_igemm<64, 64, BK, 2, 2>(p, epi, stream, tag);
-  }
+  // 128x32 for the narrow layers, else 64x64 (measured: 64x64 at 4 WGs/CU beats the 128x64 / 128x128 tiles at 4 and 8 waves,
+  // which were removed -- profiles/r05_a_gather_gemm_limits.md)
+  static const int force = getenv("BG_IGEMM_TILE") ? atoi(getenv("BG_IGEMM_TILE")) : 0;   // tuning aid: 4 = 64x64 on every layer
+  if (p.N <= 32 && force != 4) return launch_igemm<128, 32, BK, 4, 1>(p, epi, stream, tag);
+  return launch_igemm<64, 64, BK, 2, 2>(p, epi, stream, tag);
 }
 
 int run_gather(GatherParams& p, const bg_epilogue* epi, void* stream, const char* tag) {
@@ -1558,9 +1523,8 @@ int run_gather(GatherParams& p, const bg_epilogue* epi, void* stream, const char
       snprintf(name, sizeof name, "conv_thin_k_mfma_%s", tag);
       dim3 grid(tiles_x, tiles_y, p.B * p.nphase);
       bg::Launch L(stream, name, gather_flops(p), gather_bytes(p));
-      static const int staged = getenv("BG_THIN_K_STAGED") ? 1 : 0;       // the LDS-staged form (see conv_thin_k_direct_kernel)
       const size_t a_bytes_k = (size_t)p.B * p.Hs * p.Ws * p.Ck * sizeof(float);
-      if (!staged && a_bytes_k < (1ull << 31) && w_bytes < (1ull << 31)) {
+      if (a_bytes_k < (1ull << 31) && w_bytes < (1ull << 31)) {      // else the LDS-staged form (32-bit buffer offsets)
         p.a_bytes = (unsigned)a_bytes_k;
         p.w_bytes = (unsigned)w_bytes;
         if (NT == 1) bg::launch(conv_thin_k_direct_kernel<1>, grid, dim3(256), 0, L.s, p);

@@ -1546,7 +1546,8 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     pl.ksplit = (int)((M + chunk - 1) / chunk);
     return pl;
   }
-  if (strip_ok(H, W, Ci, Co, k, s) && !getenv("BG_WGRAD_NO_STRIP")) {
+  static const int no_strip = getenv("BG_WGRAD_NO_STRIP") ? 1 : 0;
+  if (strip_ok(H, W, Ci, Co, k, s) && !no_strip) {
     pl.mode = 33;                                             // strip-resident kernel, one slab per workgroup
     pl.bkp = 2;
     pl.tiles_m = Ci / 32;
@@ -1563,7 +1564,8 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     pl.always_slab = 1;
     return pl;
   }
-  if (Ci == 16 && Co == 32 && k == 5 && s == 2 && !(H & 1) && !(W & 1) && (Wo == 32 || Wo == 64) && !(Ho & 1) && !getenv("BG_NO_C16")) {
+  static const int no_c16 = getenv("BG_NO_C16") ? 1 : 0;
+  if (Ci == 16 && Co == 32 && k == 5 && s == 2 && !(H & 1) && !(W & 1) && (Wo == 32 || Wo == 64) && !(Ho & 1) && !no_c16) {
     pl.mode = 32;                                             // row-staged 16-channel kernel, persistent workgroups, one slab each
     pl.bkp = 4;
     const long nstrips = (long)B * (Ho / 2);
@@ -1573,7 +1575,8 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     pl.taps_in_grid = 0;
     return pl;
   }
-  if (thin_ci && k * Ci <= 16 && (k == 5 || k == 3) && (Co == 16 || Co == 32 || Co == 64) && Wo % 4 == 0 && !getenv("BG_WGRAD_NO_TC")) {
+  static const int no_tc = getenv("BG_WGRAD_NO_TC") ? 1 : 0;
+  if (thin_ci && k * Ci <= 16 && (k == 5 || k == 3) && (Co == 16 || Co == 32 || Co == 64) && Wo % 4 == 0 && !no_tc) {
     pl.mode = 31;                                             // row-MFMA kernel, one slab per workgroup
     pl.bkp = 4;
     const int rb = s == 2 ? 8 : 16;                          // output rows per block
@@ -1593,7 +1596,7 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     pl.tiles_m = 1;
     pl.tiles_n = bg::cdiv(Co, bn);
     pl.taps_in_grid = 0;
-  } else if (thin_co && (Ci == 16 || Ci == 32) && (k == 5 || k == 3) && k * Co <= 16 && W % 4 == 0 && !getenv("BG_WGRAD_NO_TC")) {
+  } else if (thin_co && (Ci == 16 || Ci == 32) && (k == 5 || k == 3) && k * Co <= 16 && W % 4 == 0 && !no_tc) {
     // row-MFMA kernel: one slab per workgroup, workgroups loop over blocks of kTcRows image rows
     pl.mode = 30;
     pl.bkp = 4;
@@ -1634,12 +1637,10 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
   const long base = (long)pl.tiles_m * pl.tiles_n * (pl.taps_in_grid == 1 ? kk : (pl.taps_in_grid == 2 ? k : 1));
   const long steps = (M + pl.bkp - 1) / pl.bkp;
   long want;
-  static const int old_plan = getenv("BG_WGRAD_OLD_PLAN") ? 1 : 0;
   // position-major small maps skip their all-padding chunks: workgroup lengths differ 4x between centre and corner taps, and
   // more, shorter workgroups balance better than the round model predicts (measured: G1 0.33 ms at 800 workgroups, 0.40 at 400)
-  static const int pm_pow2_plan = getenv("BG_WGRAD_PM_POW2") ? 1 : 0;
-  const bool skipping = Ho * Wo <= 16 && B >= 128 && (pm_pow2_plan ? (B & (B - 1)) == 0 : B % 128 == 0);
-  if (old_plan || pl.taps_in_grid != 1 || skipping) {     // tap-grouped kernel: measured slower with the model's single full round (0.35 vs 0.28 ms)
+  const bool skipping = Ho * Wo <= 16 && B >= 128 && B % 128 == 0;
+  if (pl.taps_in_grid != 1 || skipping) {     // tap-grouped kernel: measured slower with the model's single full round (0.35 vs 0.28 ms)
     static const int tgt_env = getenv("BG_WGRAD_TARGET") ? atoi(getenv("BG_WGRAD_TARGET")) : 0;   // tuning aid
     // ~3 workgroups per CU; the tap-grouped kernel (3 resident per CU) measured best at two full rounds (G5: 0.30 -> 0.27 ms)
     const int tgt = tgt_env ? tgt_env : (pl.taps_in_grid == 2 && M >= 200000 ? 1536 : 768);
@@ -1722,10 +1723,8 @@ int bg_conv2d_bwd_filter(const float* x, const float* dy, float* dw, int B, int 
     p.lg_b = lg2(B);
     static const int no_pm = getenv("BG_NO_POS_MAJOR") ? 1 : 0;
     // position-major: a chunk = BKP images at ONE output position, so the batch only has to be whole chunks (the critic's merged
-    // pass runs 3 x 256 = 768 samples); BG_WGRAD_PM_POW2=1 restores the power-of-two rule of rounds 1-4
-    static const int pm_pow2 = getenv("BG_WGRAD_PM_POW2") ? 1 : 0;
-    const bool b_ok = pm_pow2 ? (1 << p.lg_b) == B : B % 128 == 0;
-    if (p.pow2 && !no_pm && b_ok && B >= 128 && p.Ho * p.Wo <= 16) p.pow2 = 2;   // 8x8: the same-channel stride of position-major rows costs more than the skipped chunks save
+    // pass runs 3 x 256 = 768 samples)
+    if (p.pow2 && !no_pm && B % 128 == 0 && B >= 128 && p.Ho * p.Wo <= 16) p.pow2 = 2;   // 8x8: the same-channel stride of position-major rows costs more than the skipped chunks save
     p.x_bytes = (unsigned)((size_t)B * H * W * Cin * sizeof(float));
     p.dy_bytes = (unsigned)((size_t)p.M * Cout * sizeof(float));
   }

@@ -174,11 +174,10 @@ class Net:
         self.rng_offset = 0
         self.conv_math = "fp32"   # conv forward / data-gradient math of every call site below (ops.CONV_MATH; WGAN(conv_math=...))
         self.sync_bn = True       # data parallel: BatchNormalization statistics over the global batch
-        # statistics in the producing conv's epilogue: opt-in since round 3 -- the plain gather-GEMM variant now stores float4
+        # statistics in the producing conv's epilogue: off since round 3 -- the plain gather-GEMM variant now stores float4
         # (transposed accumulators), the statistics variant cannot, and the separate statistics pass costs less than that (C2
-        # +0.24 %, C4 +0.3 % in a same-box A/B); BGAN_FUSED_BN_STATS=1 selects the fused form
-        self.bn_bwd_read_y = os.environ.get("BGAN_BN_BWD_READ_Y") == "1"
-        self.fuse_bn_stats = os.environ.get("BGAN_FUSED_BN_STATS") == "1" and not os.environ.get("BGAN_NO_FUSED_BN_STATS")
+        # +0.24 %, C4 +0.3 % in a same-box A/B); tests set it to compare the two routes
+        self.fuse_bn_stats = False
 
     # ------------------------------------------------------------------ resources
     def context(self, B, tag="default", drop_rows=None) -> Context:
@@ -313,7 +312,7 @@ class Net:
             # instead of a tiny launch between each pair of convs (two kernel boundaries where one would do)
             fl = [(j, s2) for j, s2 in enumerate(self.stages)
                   if s2.bn is not None and s2.kind != "dense" and s2.lin.vars.get("bias") is None]
-            if 1 < len(fl) <= ops.FOLD_MAX and not os.environ.get("BGAN_NO_FOLD_MANY"):
+            if 1 < len(fl) <= ops.FOLD_MAX:
                 args = []
                 for j, s2 in fl:
                     Cj = s2.out_shape[-1]
@@ -421,11 +420,6 @@ class Net:
         x = x.to(self.device, torch.float32).contiguous()
         return self.forward(ctx, x, training=training, seed=np.random.randint(1 << 30)).clone()
 
-    def _bn_y(self, ctx, i):
-        """The saved activation the BatchNorm backward passes read for the LeakyReLU sign -- None by default: the kernels re-derive
-        the sign from z with the forward's own expression (bit-identical, one tensor less per pass).  BGAN_BN_BWD_READ_Y=1 reads it."""
-        return ctx.a[i] if self.bn_bwd_read_y else None
-
     # ------------------------------------------------------------------ backward
     def backward(self, ctx: Context, dout, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=None, dw_rows=None,
                  dx_rows=None, defer_conv_dw=False):
@@ -461,17 +455,17 @@ class Net:
                     world = dist.world_size()
                     sums = ctx.bn_sums(i, C)
                     if pending_stats is None:       # last stage: nothing above it to overlap with
-                        ops.bn_bwd_stats(gv, self._bn_y(ctx, i), ctx.z[i], M, C, ctx.mean[i], ctx.inv[i], sums, ws, lrelu_alpha=st.alpha,
+                        ops.bn_bwd_stats(gv, None, ctx.z[i], M, C, ctx.mean[i], ctx.inv[i], sums, ws, lrelu_alpha=st.alpha,
                                          gamma=st.bn.vars["gamma"], beta=st.bn.vars["beta"])
                         pending_stats = dist.all_reduce_sum_async(sums)
                     pending_stats.wait()            # issued before the filter gradient of the stage above: it travelled meanwhile
                     pending_stats = None
-                    ops.bn_bwd_apply(gv, self._bn_y(ctx, i), ctx.z[i], dz, M, M * world, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], sums,
+                    ops.bn_bwd_apply(gv, None, ctx.z[i], dz, M, M * world, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], sums,
                                      lrelu_alpha=st.alpha, beta=st.bn.vars["beta"])
                     if need_dw:     # the sums are already global: pre-divide so the flat gradient SUM all-reduce restores them
                         ops.bn_param_grads(sums, C, 1.0 / world, dg, db)
                 else:
-                    ops.bn_train_bwd(gv, self._bn_y(ctx, i), ctx.z[i], dz, M, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], dg, db, ws,
+                    ops.bn_train_bwd(gv, None, ctx.z[i], dz, M, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], dg, db, ws,
                                      lrelu_alpha=st.alpha, beta=st.bn.vars["beta"])
             elif st.act == "lrelu":
                 if g_is_dz:
@@ -575,7 +569,7 @@ class Net:
                 gp = tgt.view(B, *prev.out_shape)
                 Mp = gp.numel() // Cp
                 sums = ctx.bn_sums(i - 1, Cp)
-                ops.bn_bwd_stats(gp, self._bn_y(ctx, i - 1), ctx.z[i - 1], Mp, Cp, ctx.mean[i - 1], ctx.inv[i - 1], sums,
+                ops.bn_bwd_stats(gp, None, ctx.z[i - 1], Mp, Cp, ctx.mean[i - 1], ctx.inv[i - 1], sums,
                                  self.workspace(ops._lib.load().bg_bn_workspace_bytes(Mp, Cp)), lrelu_alpha=prev.alpha,
                                  gamma=prev.bn.vars["gamma"], beta=prev.bn.vars["beta"])
                 pending_stats = dist.all_reduce_sum_async(sums)

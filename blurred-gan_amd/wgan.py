@@ -20,12 +20,13 @@ from .gaussian_blur import Variable
 from .layers import Sequential, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
 
-_KEY_ENV = ("BGAN_NO_FUSED_BLUR3", "BGAN_NO_FOLD_MANY", "BGAN_NO_FUSED_BN_STATS", "BG_BLUR_NO_ROWS", "BG_BLUR_NO_PANEL", "BG_BLUR_PANEL16", "BG_WGRAD_NO_STRIP")
+# the switches the engine / the library read per call that shape a step's launch list ("per call (step key)")
+_KEY_ENV = ("BGAN_NO_FUSED_BLUR3", "BGAN_NO_FUSED_BN_STATS", "BG_BLUR_BAND_LD", "BG_BLUR_NO_ROWS", "BG_BLUR_NO_PANEL", "BG_BLUR_PANEL16")
 
 
 def _env_switches():
-    """Dispatch switches that the engine / the library read per call and that change a step's launch list: part of the step-program
-    key, so flipping one mid-run records a new program instead of replaying a stale launch list."""
+    """The per-call switches change a step's launch list: part of the step-program key, so flipping one mid-run records a new
+    program instead of replaying a stale launch list."""
     return tuple(os.environ.get(k) for k in _KEY_ENV)
 
 
@@ -152,10 +153,10 @@ class WGAN:
         self._met_event = None
         self.sync_batchnorm = sync_batchnorm  # DP: generator BN statistics over the global batch (False = per replica)
         # critic step: [fakes; reals] and x-hat in one 3B-sample forward / backward (False: two passes, as the reference orders them)
-        self.merge_critic_passes = merge_critic_passes and not os.environ.get("BGAN_NO_MERGED_CRITIC")
+        self.merge_critic_passes = merge_critic_passes
         # the penalty's second-order filter gradients ride in the merged pass's own filter-gradient launches
         # (engine.Net.gp_second_order_merged); needs the merged critic pass
-        self.merge_gp_filter_gradients = merge_gp_filter_gradients and not os.environ.get("BGAN_NO_MERGED_GP_WGRAD")
+        self.merge_gp_filter_gradients = merge_gp_filter_gradients
         # a sample whose critic input-gradient is exactly zero makes the penalty's second-order seed (n-1)/n * g = NaN, in the
         # reference too (tf.norm's gradient at 0); True takes the subgradient 0 for that sample instead
         self.gp_zero_norm_guard = gp_zero_norm_guard
@@ -310,7 +311,7 @@ class WGAN:
         return (kind, tuple(reals.shape), reals.data_ptr(), D.blur_n_taps(), G.store.tr_dirty, D.store.tr_dirty, self.merge_critic_passes,
                 self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
                 self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
-                G.store.n_train, D.store.n_train, G.bn_bwd_read_y, G.conv_math, D.conv_math, _env_switches(), hp,
+                G.store.n_train, D.store.n_train, G.conv_math, D.conv_math, _env_switches(), hp,
                 self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
 
     @staticmethod

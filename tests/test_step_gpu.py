@@ -355,8 +355,8 @@ def test_merged_penalty_filter_gradients_equal_the_separate_launches(arch, B):
 
 @pytest.mark.parametrize("arch,B", [("celeba64", 64), ("celeba128", 4)])
 def test_fused_batchnorm_statistics_equal_the_separate_pass(arch, B):
-    """BatchNorm batch statistics left by the producing conv's epilogue (engine.Net.fuse_bn_stats, opt-in since round 3:
-    BGAN_FUSED_BN_STATS=1) against the separate statistics pass (the default): the same generator gradients and moving statistics up
+    """BatchNorm batch statistics left by the producing conv's epilogue (engine.Net.fuse_bn_stats, off by default since round 3)
+    against the separate statistics pass (the default): the same generator gradients and moving statistics up
     to summation order -- which the BatchNorm backward's cancellation amplifies to the level of the float32 oracle's own
     deviation from float64 (helpers.GRAD_L2["g"]): the bound on the gradients is that one, the statistics themselves agree to 1e-5."""
     ref = None
