@@ -249,11 +249,15 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (BM == 64 && BN == 64 && !S
   const __amdgpu_buffer_rsrc_t rsNull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, 0, 0x00020000);
   unsigned a_voff[AP];                                   // byte offset of the row's quad at the current tap (bit 31: poisoned)
   unsigned g_woff = 0;                                   // weight offset of the current tap, without the channel chunk (scalar)
-  int g_tp_v = taplist[min(g_tq, ntaps_c - 1)];          // the NEXT tap's packed entry, read one tap ahead of its use (no LDS wait then)
+  // A workgroup without a live tap (every phase of its group empty: three of the four phases of a 1x1 stride-2 data gradient) runs
+  // no K step and all its loads go through the null descriptor; the tap index is clamped to entry 0 (in range, its contents
+  // unused), not to -1.
+  const int t_last = max(ntaps_c - 1, 0);
+  int g_tp_v = taplist[min(g_tq, t_last)];               // the NEXT tap's packed entry, read one tap ahead of its use (no LDS wait then)
   auto new_tap = [&]() {                                 // wave-uniform: runs when the load stream moves to another tap
-    const int tq = min(g_tq, ntaps_c - 1);
+    const int tq = min(g_tq, t_last);
     const int tp = __builtin_amdgcn_readfirstlane(g_tp_v);
-    g_tp_v = taplist[min(g_tq + 1, ntaps_c - 1)];
+    g_tp_v = taplist[min(g_tq + 1, t_last)];
     const int dy = bg::tap_dy(tp), dx = bg::tap_dx(tp);
     const unsigned tapoff = (unsigned)(((dy * p.Ws + dx) * p.Ck) * 4);
     g_woff = (unsigned)((bg::tap_wi(tp) * p.N * p.Ck) * 4);
@@ -542,6 +546,7 @@ __global__ __launch_bounds__(256) void conv_thin_n_patch_kernel(const GatherPara
     dmin_y = min(dmin_y, dy); dmax_y = max(dmax_y, dy);
     dmin_x = min(dmin_x, dx); dmax_x = max(dmax_x, dx);
   }
+  if (g.ntaps == 0) dmin_y = dmax_y = dmin_x = dmax_x = 0;   // a phase without taps has no halo (not the inverted start values)
   const int PH = (kThinTH - 1) * p.ss + (dmax_y - dmin_y) + 1;
   const int PW = (kThinTW - 1) * p.ss + (dmax_x - dmin_x) + 1;
   const int sy0 = a0 * p.ss + dmin_y, sx0 = x0 * p.ss + dmin_x;
@@ -827,6 +832,7 @@ __global__ __launch_bounds__(256) void conv_thin_k_mfma_kernel(const GatherParam
     dmin_y = min(dmin_y, dy); dmax_y = max(dmax_y, dy);
     dmin_x = min(dmin_x, dx); dmax_x = max(dmax_x, dx);
   }
+  if (g.ntaps == 0) dmin_y = dmax_y = dmin_x = dmax_x = 0;   // a phase without taps has no halo (not the inverted start values)
   const int PH = (kTkTH - 1) * p.ss + (dmax_y - dmin_y) + 1;
   const int PW = (kTkTW - 1) * p.ss + (dmax_x - dmin_x) + 1;
   const int KF = g.ntaps * Ck, KFP = (KF + 1) & ~1;
@@ -1428,6 +1434,7 @@ int run_gather(GatherParams& p, const bg_epilogue* epi, void* stream, const char
         const int dy = bg::tap_dy(p.ph[i].tap[t]), dx = bg::tap_dx(p.ph[i].tap[t]);
         mny = std::min(mny, dy); mxy = std::max(mxy, dy); mnx = std::min(mnx, dx); mxx = std::max(mxx, dx);
       }
+      if (p.ph[i].ntaps == 0) mny = mxy = mnx = mxx = 0;      // a phase without taps (k = 1, stride 2): no halo, as in the kernel
       const size_t PH = (kThinTH - 1) * p.ss + (mxy - mny) + 1, PW = (kThinTW - 1) * p.ss + (mxx - mnx) + 1;
       lds = std::max(lds, PH * PW * (size_t)(p.Ck + 4) * sizeof(float));
       tiles_x = std::max(tiles_x, (int)bg::cdiv(p.ph[i].Wa, kThinTW));
@@ -1513,6 +1520,7 @@ int run_gather(GatherParams& p, const bg_epilogue* epi, void* stream, const char
         const int dy = bg::tap_dy(p.ph[i].tap[t]), dx = bg::tap_dx(p.ph[i].tap[t]);
         mny = std::min(mny, dy); mxy = std::max(mxy, dy); mnx = std::min(mnx, dx); mxx = std::max(mxx, dx);
       }
+      if (p.ph[i].ntaps == 0) mny = mxy = mnx = mxx = 0;      // a phase without taps (k = 1, stride 2): no halo, as in the kernel
       const size_t PH = (kTkTH - 1) * p.ss + (mxy - mny) + 1, PW = (kTkTW - 1) * p.ss + (mxx - mnx) + 1;
       lds = std::max(lds, ((size_t)kTkMaxKF * 32 * NT + PH * PW * p.Ck) * sizeof(float));
       tiles_x = std::max(tiles_x, (int)bg::cdiv(p.ph[i].Wa, kTkTW));

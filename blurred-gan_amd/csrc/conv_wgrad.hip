@@ -1526,6 +1526,17 @@ inline bool strip_ok(int H, int W, int Ci, int Co, int k, int s) {
   return Ho % (64 / Wo) == 0;
 }
 
+// LDS of the row-MFMA kernels (modes 31 / 30): the staged rows of a block, or the cross-wave reduction if that is larger.  The plan
+// and the launch both go by these: a row too wide for 64 KB takes the generic thin kernels (modes 10..12 / 20..22) instead.
+constexpr size_t kRowLdsMax = 64 * 1024;
+inline int thin_ci_rows(int s) { return s == 2 ? 8 : 16; }   // output rows per block of the thin-Ci kernel
+inline size_t thin_ci_lds(int W, int Ci, int Co, int k, int s) {
+  return std::max((size_t)((thin_ci_rows(s) - 1) * s + k) * ((size_t)W * Ci + 2 * kTiHalo), (size_t)k * (Co / 16) * 4 * 64) * sizeof(float);
+}
+inline size_t thin_co_lds(int W, int Ci, int Co, int k) {
+  return std::max((size_t)(kTcRows + k - 1) * ((size_t)W * Co + 2 * kTcHalo), (size_t)4 * k * (Ci / 16) * 4 * 64) * sizeof(float);
+}
+
 WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
   WgradPlan pl{};
   int Ho, Wo, pt, pp;
@@ -1576,10 +1587,11 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     return pl;
   }
   static const int no_tc = getenv("BG_WGRAD_NO_TC") ? 1 : 0;
-  if (thin_ci && k * Ci <= 16 && (k == 5 || k == 3) && (Co == 16 || Co == 32 || Co == 64) && Wo % 4 == 0 && !no_tc) {
+  if (thin_ci && k * Ci <= 16 && (k == 5 || k == 3) && (Co == 16 || Co == 32 || Co == 64) && Wo % 4 == 0 && !no_tc &&
+      thin_ci_lds(W, Ci, Co, k, s) <= kRowLdsMax) {
     pl.mode = 31;                                             // row-MFMA kernel, one slab per workgroup
     pl.bkp = 4;
-    const int rb = s == 2 ? 8 : 16;                          // output rows per block
+    const int rb = thin_ci_rows(s);                          // output rows per block
     const long nblocks = (long)B * bg::cdiv(Ho, rb);
     pl.ksplit = (int)std::max<long>(2, std::min<long>(nblocks, 1024));
     pl.chunk = (int)nblocks;
@@ -1596,7 +1608,8 @@ WgradPlan plan_wgrad(int B, int H, int W, int Ci, int Co, int k, int s) {
     pl.tiles_m = 1;
     pl.tiles_n = bg::cdiv(Co, bn);
     pl.taps_in_grid = 0;
-  } else if (thin_co && (Ci == 16 || Ci == 32) && (k == 5 || k == 3) && k * Co <= 16 && W % 4 == 0 && !no_tc) {
+  } else if (thin_co && (Ci == 16 || Ci == 32) && (k == 5 || k == 3) && k * Co <= 16 && W % 4 == 0 && !no_tc &&
+             thin_co_lds(W, Ci, Co, k) <= kRowLdsMax) {
     // row-MFMA kernel: one slab per workgroup, workgroups loop over blocks of kTcRows image rows
     pl.mode = 30;
     pl.bkp = 4;
@@ -1786,11 +1799,11 @@ int bg_conv2d_bwd_filter(const float* x, const float* dy, float* dw, int B, int 
     rc = L.done("conv_wgrad_c16_kernel");
   } else if (pl.mode == 31) {
     bg::Launch L(stream, "conv_wgrad_mfma_thin_ci", flops, abytes);
-    const int rb = stride == 2 ? 8 : 16;
+    const int rb = thin_ci_rows(stride);
     const int bpi = (int)bg::cdiv(p.Ho, rb), nblocks = B * bpi;
     const int nt = Cout / 16;
-    const size_t lds = std::max((size_t)((rb - 1) * stride + ksize) * (W * Cin + 2 * kTiHalo), (size_t)ksize * nt * 4 * 64) * sizeof(float);
-    BG_REQUIRE(lds <= 64 * 1024, BG_ERR_UNSUPPORTED, "bg_conv2d_bwd_filter: thin-Ci row kernel needs %zu bytes of LDS", lds);
+    const size_t lds = thin_ci_lds(W, Cin, Cout, ksize, stride);
+    BG_REQUIRE(lds <= kRowLdsMax, BG_ERR_UNSUPPORTED, "bg_conv2d_bwd_filter: thin-Ci row kernel needs %zu bytes of LDS", lds);
 #define BG_TI(NTv, Kv) bg::launch((conv_wgrad_thin_ci_kernel<NTv, Kv>), dim3(pl.ksplit), dim3(256), lds, L.s, p, nblocks, bpi, rb)
     if (ksize == 5) { if (nt == 1) BG_TI(1, 5); else if (nt == 2) BG_TI(2, 5); else BG_TI(4, 5); }
     else { if (nt == 1) BG_TI(1, 3); else if (nt == 2) BG_TI(2, 3); else BG_TI(4, 3); }
@@ -1800,8 +1813,8 @@ int bg_conv2d_bwd_filter(const float* x, const float* dy, float* dw, int B, int 
     bg::Launch L(stream, "conv_wgrad_mfma_thin_co", flops, abytes);
     const int bpi = (int)bg::cdiv(H, kTcRows), nblocks = B * bpi;
     const int mt = Cin / 16;
-    const size_t lds = std::max((size_t)(kTcRows + ksize - 1) * (W * Cout + 2 * kTcHalo), (size_t)4 * ksize * mt * 4 * 64) * sizeof(float);
-    BG_REQUIRE(lds <= 64 * 1024, BG_ERR_UNSUPPORTED, "bg_conv2d_bwd_filter: thin-Co row kernel needs %zu bytes of LDS", lds);
+    const size_t lds = thin_co_lds(W, Cin, Cout, ksize);
+    BG_REQUIRE(lds <= kRowLdsMax, BG_ERR_UNSUPPORTED, "bg_conv2d_bwd_filter: thin-Co row kernel needs %zu bytes of LDS", lds);
     if (ksize == 5 && mt == 2) bg::launch((conv_wgrad_thin_co_kernel<2, 5>), dim3(pl.ksplit), dim3(256), lds, L.s, p, nblocks, bpi);
     else if (ksize == 5) bg::launch((conv_wgrad_thin_co_kernel<1, 5>), dim3(pl.ksplit), dim3(256), lds, L.s, p, nblocks, bpi);
     else if (mt == 2) bg::launch((conv_wgrad_thin_co_kernel<2, 3>), dim3(pl.ksplit), dim3(256), lds, L.s, p, nblocks, bpi);

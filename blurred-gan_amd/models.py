@@ -2,8 +2,9 @@
 
 ``arch``: "mnist" (demo_mnist.py:48-86), "celeba128" (demo_celeba.py:51-124, verbatim), "celeba64"
 (build-side definition for BASELINE.json's 64x64 configs: the 128 stack minus its outermost stage on each
-side, SURVEY.md 8a "Architecture note"), plus two small test geometries ("tiny": MFMA-tileable channel
-counts on 8x8x3 images; "tiny_mnist": odd channel counts, 12x12x1, ConvT with fused tanh)."""
+side, SURVEY.md 8a "Architecture note"), plus small test geometries ("tiny": MFMA-tileable channel
+counts on 8x8x3 images; "tiny_mnist": odd channel counts, 12x12x1, ConvT with fused tanh; "tiny_k3": the "tiny"
+stacks with 3x3 kernels -- every other architecture uses the demos' 5x5)."""
 from __future__ import annotations
 
 from . import layers
@@ -14,18 +15,21 @@ _G = {  # base_hw, dense_ch, [(filters, stride, activation)], last_conv_filters
     "celeba64": (4, 512, [(512, 1, None), (256, 2, None), (128, 2, None), (64, 2, None), (32, 2, None)], 3),
     "tiny": (2, 32, [(32, 1, None), (16, 2, None), (16, 2, None)], 3),
     "tiny_mnist": (3, 8, [(8, 1, None), (4, 2, None), (1, 2, "tanh")], None),
+    "tiny_k3": (2, 32, [(32, 1, None), (16, 2, None), (16, 2, None)], 3),
 }
 _D = {"mnist": [64, 128], "celeba128": [16, 32, 64, 128, 256, 512], "celeba64": [32, 64, 128, 256, 512],
-      "tiny": [16, 32], "tiny_mnist": [4, 8]}
+      "tiny": [16, 32], "tiny_mnist": [4, 8], "tiny_k3": [16, 32]}
+KSIZE = {"tiny_k3": 3}      # conv kernel size per architecture; 5 where not listed
 IMAGE_SHAPE = {"mnist": (28, 28, 1), "celeba128": (128, 128, 3), "celeba64": (64, 64, 3), "tiny": (8, 8, 3),
-               "tiny_mnist": (12, 12, 1)}
-LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mnist": 6}
+               "tiny_mnist": (12, 12, 1), "tiny_k3": (8, 8, 3)}
+LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mnist": 6, "tiny_k3": 10}
 
 
 class DCGANGenerator(layers.Sequential):
     def __init__(self, latent_size=None, arch="celeba128", *args, **kwargs):
         super().__init__(*args, **kwargs)
         base, ch, convt, last = _G[arch]
+        k = KSIZE.get(arch, 5)
         self.latent_size = latent_size or LATENT[arch]
         self.add(layers.Dense(base * base * ch, use_bias=False, input_shape=(self.latent_size,)))
         self.add(layers.BatchNormalization())
@@ -34,14 +38,14 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, base, base, ch)
         hw = base
         for filters, stride, act in convt:
-            self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding="same", use_bias=False, activation=act))
+            self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=False, activation=act))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
             if act is None:
                 self.add(layers.BatchNormalization())
                 self.add(layers.LeakyReLU())
         if last is not None:
-            self.add(layers.Conv2D(last, (5, 5), padding="same", use_bias=False, activation="tanh"))
+            self.add(layers.Conv2D(last, (k, k), padding="same", use_bias=False, activation="tanh"))
         assert self.output_shape == (None,) + IMAGE_SHAPE[arch], self.output_shape
 
 
@@ -50,7 +54,7 @@ class DCGANDiscriminator(layers.Sequential):
         super().__init__(*args, **kwargs)
         for i, c in enumerate(_D[arch]):
             kw = dict(input_shape=list(IMAGE_SHAPE[arch])) if i == 0 else {}
-            self.add(layers.Conv2D(c, 5, strides=2, padding="same", **kw))
+            self.add(layers.Conv2D(c, KSIZE.get(arch, 5), strides=2, padding="same", **kw))
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
         self.add(layers.Flatten())

@@ -15,23 +15,26 @@ import numpy as np
 from . import np_ops as O
 
 
-def _g_stack(base_hw, dense_ch, convt, last):
+KSIZE = {"tiny_k3": 3}     # conv kernel size per architecture; 5 where not listed
+
+
+def _g_stack(base_hw, dense_ch, convt, last, k=5):
     spec = [dict(type="dense", units=base_hw * base_hw * dense_ch, use_bias=False),
             dict(type="bn"), dict(type="lrelu"),
             dict(type="reshape", shape=(base_hw, base_hw, dense_ch))]
     for filters, stride, act in convt:
-        spec.append(dict(type="convT", filters=filters, k=5, stride=stride, use_bias=False, activation=act))
+        spec.append(dict(type="convT", filters=filters, k=k, stride=stride, use_bias=False, activation=act))
         if act is None:
             spec += [dict(type="bn"), dict(type="lrelu")]
     if last is not None:
-        spec.append(dict(type="conv", filters=last, k=5, stride=1, use_bias=False, activation="tanh"))
+        spec.append(dict(type="conv", filters=last, k=k, stride=1, use_bias=False, activation="tanh"))
     return spec
 
 
-def _d_stack(chs):
+def _d_stack(chs, k=5):
     spec = []
     for c in chs:
-        spec += [dict(type="conv", filters=c, k=5, stride=2, use_bias=True, activation=None),
+        spec += [dict(type="conv", filters=c, k=k, stride=2, use_bias=True, activation=None),
                  dict(type="lrelu"), dict(type="dropout", rate=0.3)]
     spec += [dict(type="flatten"), dict(type="dense", units=1, use_bias=True)]
     return spec
@@ -50,6 +53,8 @@ def generator_spec(name):
         return _g_stack(2, 32, [(32, 1, None), (16, 2, None), (16, 2, None)], 3)
     if name == "tiny_mnist":  # test-only: ConvT with fused tanh and 1 channel, odd sizes
         return _g_stack(3, 8, [(8, 1, None), (4, 2, None), (1, 2, "tanh")], None)
+    if name == "tiny_k3":    # test-only: the "tiny" stack with 3x3 kernels
+        return _g_stack(2, 32, [(32, 1, None), (16, 2, None), (16, 2, None)], 3, k=KSIZE[name])
     raise KeyError(name)
 
 
@@ -64,15 +69,17 @@ def discriminator_spec(name):
         return _d_stack([16, 32])
     if name == "tiny_mnist":
         return _d_stack([4, 8])
+    if name == "tiny_k3":
+        return _d_stack([16, 32], k=KSIZE[name])
     raise KeyError(name)
 
 
 def image_shape(name):
     return {"mnist": (28, 28, 1), "celeba128": (128, 128, 3), "celeba64": (64, 64, 3),
-            "tiny": (8, 8, 3), "tiny_mnist": (12, 12, 1)}[name]
+            "tiny": (8, 8, 3), "tiny_mnist": (12, 12, 1), "tiny_k3": (8, 8, 3)}[name]
 
 
-LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mnist": 6}
+LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mnist": 6, "tiny_k3": 10}
 
 
 # ----------------------------------------------------------------------------

@@ -39,6 +39,18 @@ for B in (1, 3, 64, 128, 256, 768):
         lib.bg_conv2d_bwd_filter_workspace_bytes(B, H, W, Ci, Co, 5, s)
         lib.bg_conv2d_splitk_workspace_bytes(0, B, H, W, Ci, Co, 5, s)
         lib.bg_conv2d_splitk_workspace_bytes(1, B, H, W, Ci, Co, 5, s)
+    # every kernel size of the ABI (a 1x1 stride-2 data gradient has three tap-less phases), rows wider than the row-MFMA filter
+    # gradients stage (their plan must fall back, not only their launch), 1x1 and 2x2 maps
+    for ksize in (1, 3, 5):
+        for (H, W, Ci, Co, s) in ((64, 64, 3, 32, 2), (32, 32, 32, 64, 2), (16, 16, 64, 128, 2), (8, 8, 128, 256, 2), (4, 4, 256, 512, 2),
+                                  (4, 4, 512, 512, 1), (128, 128, 16, 32, 2), (64, 64, 32, 3, 1), (28, 28, 1, 64, 2), (7, 9, 32, 64, 1), (5, 5, 8, 4, 2),
+                                  (16, 320, 3, 32, 2), (8, 512, 3, 16, 2), (8, 320, 32, 3, 1), (8, 256, 4, 32, 1), (16, 16, 5, 32, 1), (16, 16, 32, 5, 1),
+                                  (1, 1, 32, 64, 1), (1, 1, 32, 64, 2), (2, 2, 256, 512, 2), (2, 2, 3, 32, 2), (1, 1, 3, 3, 2), (2, 2, 1024, 64, 1)):
+            nb = lib.bg_conv2d_bwd_filter_workspace_bytes(B, H, W, Ci, Co, ksize, s)
+            assert nb % (4 * ksize * ksize * Ci * Co) == 0, (B, H, W, Ci, Co, ksize, s, nb)
+            for bwd in (0, 1):
+                nk = lib.bg_conv2d_splitk_workspace_bytes(bwd, B, H, W, Ci, Co, ksize, s)
+                assert nk % (4 * B * (H if bwd else -(-H // s)) * (W if bwd else -(-W // s)) * (Ci if bwd else Co)) == 0, (bwd, B, H, W, Ci, Co, ksize, s, nk)
     for (H, W, Cc) in ((64, 64, 3), (28, 28, 1), (128, 128, 3), (256, 256, 3), (218, 178, 3), (5, 7, 2), (130, 66, 4), (40, 24, 8)):
         for T in (3, 13, 31, 65, 143, 255):
             lib.bg_blur_workspace_bytes(B, H, W, Cc, T)

@@ -82,6 +82,31 @@ def test_conv_family_vs_torch_and_adjoint(H, W, s):
     np.testing.assert_allclose(dw, wt.grad.numpy(), atol=1e-10)
 
 
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("H,W,s", [(1, 1, 1), (1, 1, 2), (2, 2, 2), (3, 5, 2), (4, 4, 1), (7, 7, 2), (6, 9, 1), (8, 8, 2), (5, 8, 2)])
+def test_conv_family_at_kernel_sizes_1_and_3(H, W, s, k):
+    """The oracle is the reference of tests/test_conv_ksize_gpu.py at k = 1 and 3: same checks as above (1x1 maps and odd sizes
+    included; at k = 1, stride 2 three of the four sub-pixel phases of the data gradient receive nothing)."""
+    rng = np.random.default_rng(3)
+    x = rng.normal(size=(2, H, W, 3))
+    w = rng.normal(size=(k, k, 3, 4))
+    y = O.conv2d_fwd(x, w, s)
+    np.testing.assert_allclose(y, T.conv2d(torch.from_numpy(x), torch.from_numpy(w), s).numpy(), atol=1e-11)
+    dy = rng.normal(size=y.shape)
+    dx = O.conv2d_bwd_data(dy, w, s, (H, W))
+    dw = O.conv2d_bwd_filter(x, dy, s, k)
+    assert abs((y * dy).sum() - (x * dx).sum()) < 1e-9
+    assert abs((y * dy).sum() - (w * dw).sum()) < 1e-9
+    assert abs((x * dx).sum() - (w * dw).sum()) < 1e-9
+    xt = torch.from_numpy(x).requires_grad_(True)
+    wt = torch.from_numpy(w).requires_grad_(True)
+    (T.conv2d(xt, wt, s) * torch.from_numpy(dy)).sum().backward()
+    np.testing.assert_allclose(dx, xt.grad.numpy(), atol=1e-10)
+    np.testing.assert_allclose(dw, wt.grad.numpy(), atol=1e-10)
+    if k == 1 and s == 2:
+        assert not dx[:, 1::2].any() and not dx[:, :, 1::2].any()
+
+
 @pytest.mark.parametrize("h,s", [(4, 2), (7, 2), (4, 1), (7, 1), (3, 2)])
 def test_conv_transpose_geometry_and_torch(h, s):
     """Pins the reference's shape asserts (demo_celeba.py:60-93, demo_mnist.py:58-71): SAME/stride-s
@@ -197,7 +222,7 @@ def _to_t(rnd):
     return out
 
 
-@pytest.mark.parametrize("arch,B,std", [("tiny", 4, 0.05), ("tiny", 3, 1.2), ("tiny_mnist", 4, 0.7)])
+@pytest.mark.parametrize("arch,B,std", [("tiny", 4, 0.05), ("tiny", 3, 1.2), ("tiny_mnist", 4, 0.7), ("tiny_k3", 4, 0.9)])
 def test_step_gradients_match_torch_autograd_fp64(arch, B, std):
     """Explicit formulas (incl. the GP second-order closed form, Q1 vector loss, Q4 inference-BN in the
     D-step) == torch autograd with create_graph double backward, in float64."""

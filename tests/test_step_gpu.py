@@ -37,7 +37,8 @@ def _make(arch, B, std, seed=0, gbs=None, **kw):
 
 @pytest.mark.parametrize("arch,B,std", [("tiny", 4, 0.05), ("tiny", 5, 1.2), ("tiny_mnist", 4, 0.7), ("mnist", 3, 0.05),
                                         ("celeba64", 2, 1.0), ("celeba128", 2, 2.0),      # the headline architectures, every layer shape of C2 / C4
-                                        ("celeba64", 64, 5.0)])     # ... and at a batch that takes the position-major / tap-skipping / split-K paths
+                                        ("celeba64", 64, 5.0),      # ... and at a batch that takes the position-major / tap-skipping / split-K paths
+                                        ("tiny_k3", 4, 0.9)])       # the "tiny" stacks with 3x3 kernels: the step at a kernel size other than 5
 def test_gradients_match_oracle(arch, B, std):
     gan, st, reals, rng = _make(arch, B, std, gbs=B + 1)
     rnd = S.draw_randomness(arch, B, rng, np.float64)
@@ -82,7 +83,7 @@ def test_gradients_match_oracle(arch, B, std):
     assert abs(got["std"] - std) < 1e-7 and got["loss"] == 0.0
 
 
-@pytest.mark.parametrize("arch,B,std", [("tiny", 4, 0.9), ("tiny_mnist", 3, 0.05)])
+@pytest.mark.parametrize("arch,B,std", [("tiny", 4, 0.9), ("tiny_mnist", 3, 0.05), ("tiny_k3", 4, 0.9)])
 def test_three_training_steps_match_oracle(arch, B, std):
     """Weights, Adam slots, BN moving statistics and counters after 3 full steps (float32 oracle vs HIP)."""
     gan, st64, reals, rng = _make(arch, B, std)
