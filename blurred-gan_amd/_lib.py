@@ -90,6 +90,7 @@ SIGNATURES = {
     "bg_sgd_f32": (_i, [_p, _p, _p, _z, _f, _f, _i, _p]),
     "bg_rmsprop_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _i, _p]),
     "bg_adam_amsgrad_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _p]),
+    "bg_ema_f32": (_i, [_p, _p, _z, _p, _p, _z, _f, _p]),
     "bg_uniform_f32": (_i, [_p, _z, _u64, _u64, _p]),
     "bg_keep_mask_u8": (_i, [_p, _z, _f, _u64, _u64, _p]),
     "bg_program_create": (_i, [C.POINTER(_p), _i]),
@@ -114,7 +115,7 @@ SIGNATURES = {
 }
 
 COMM_ID_BYTES = 128
-BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR = 1, 2, 3      # include/bgan.h BG_BIND_*
+BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*
 
 _lib = None
 

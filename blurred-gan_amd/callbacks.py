@@ -135,8 +135,10 @@ class AdaptiveBlurController(Callback):
 class GenerateSampleGridCallback(ExecuteEveryNExamplesCallback):
     """callbacks.py:209-236: an 8x8 grid of samples from fixed latents, written as PNG (PIL, no matplotlib)."""
 
-    def __init__(self, log_dir: str, show_blurred_samples=True, every_n_examples=1000, also_save_files=True):
+    def __init__(self, log_dir: str, show_blurred_samples=True, every_n_examples=1000, also_save_files=True, use_ema=None):
+        """``use_ema``: sample from the averaged generator (``WGAN(generator_ema=...)``); None = when the model has one."""
         self.log_dir = log_dir
+        self.use_ema = use_ema
         self.show_blurred_samples = show_blurred_samples
         super().__init__(n=every_n_examples)
         self.also_save_files = also_save_files
@@ -151,7 +153,10 @@ class GenerateSampleGridCallback(ExecuteEveryNExamplesCallback):
 
     def make_grid(self, *args):
         from .utils import normalize_images
-        samples = self.model.generate_samples(self.latents, training=False)
+        use_ema = self.use_ema
+        if use_ema is None:
+            use_ema = getattr(self.model, "generator_ema", None) is not None
+        samples = self.model.generate_samples(self.latents, training=False, **({"ema": True} if use_ema else {}))
         if self.show_blurred_samples and hasattr(self.model, "blur"):
             samples = self.model.blur(samples)
         s = normalize_images(samples).clamp(0, 1).cpu().numpy()

@@ -2,7 +2,10 @@
 (demo_mnist.py:145-163, callbacks.py:239-246).  One ``.npz`` per checkpoint holding both networks' variables
 (weights + BN moving statistics), both optimizers (class, ``get_config()`` as JSON, learning rate, step count and every slot
 buffer in use), ``n_img``, ``n_batches``, ``blur.std`` and the positions of the step's random streams (latents / alpha /
-dropout), so a resumed run continues the uninterrupted one.  A checkpoint restores only into a model whose optimizers have the
+dropout), so a resumed run continues the uninterrupted one.  With weight averaging on (``WGAN(generator_ema=...)``) the averaged
+generator's two buffers, its update count and its schedule are saved too (``g_ema_*``); a checkpoint without them restores into
+such a model with the averages reset to the restored live weights (and a warning), one with them into a model without the
+feature, which ignores them.  A checkpoint restores only into a model whose optimizers have the
 same class and static configuration (``ValueError`` otherwise); one written before optimizers were recorded (``m`` / ``v``
 only) is a default Adam's.
 
@@ -14,6 +17,7 @@ from __future__ import annotations
 import json
 import os
 import re
+import warnings
 
 import numpy as np
 import torch
@@ -93,6 +97,12 @@ class CheckpointManager:
             lr = opt.learning_rate
             d[f"{tag}_opt_lr"] = np.float64(lr if not callable(lr) else np.nan)      # a schedule lives in the config
             d[f"{tag}_rng_offset"] = np.int64(int(model.net().rng_offset))        # dropout-mask stream of this network
+        if getattr(g, "generator_ema", None) is not None:
+            st = g.generator_ema.store
+            d["g_ema_theta"] = st.theta.cpu().numpy()
+            d["g_ema_state"] = st.state.cpu().numpy()
+            d["g_ema_updates"] = np.int64(g.generator_ema_updates)
+            d["g_ema_config"] = np.str_(json.dumps(g.generator_ema_config.get_config()))
         return d
 
     def save(self, checkpoint_number=None):
@@ -154,4 +164,17 @@ class CheckpointManager:
             if f"{tag}_rng_offset" in d.files:
                 model.net().rng_offset = int(d[f"{tag}_rng_offset"])
             st.tr_dirty = True
+        if getattr(g, "generator_ema", None) is not None:
+            if "g_ema_theta" in d.files:
+                st = g.generator_ema.store
+                st.theta.copy_(torch.from_numpy(d["g_ema_theta"]))
+                st.state.copy_(torch.from_numpy(d["g_ema_state"]))
+                st.tr_dirty = True
+                g.generator_ema_updates = int(d["g_ema_updates"])
+            else:
+                g.reset_generator_ema()          # the live weights are in place
+                if not getattr(g, "_warned_no_ema", False):          # once per model
+                    g._warned_no_ema = True
+                    warnings.warn(f"{path} holds no averaged generator: the averages start from the restored live weights, "
+                                  "update count 0", RuntimeWarning, stacklevel=2)
         return path

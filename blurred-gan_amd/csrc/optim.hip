@@ -3,6 +3,7 @@
 // computes the step's learning rate (schedule, inverse-time decay, Adam's bias correction); the kernels apply the elementwise
 // rule over a model's flat trainable buffer.  One kernel per static variant (momentum / Nesterov / centered are template
 // parameters); the body moves float4 quads in a grid-stride loop, and the n % 4 last elements go through a scalar tail.
+// bg_ema_f32 (the averaged generator's update, tf.train.ExponentialMovingAverage) sweeps two buffers the same way in one launch.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -99,6 +100,35 @@ __global__ __launch_bounds__(kT) void adam_amsgrad_kernel(float* theta, float* m
   });
 }
 
+// Weight averaging (TF assign_moving_average): avg -= w * (avg - theta), w = 1 - decay.  The same sweep shape over one buffer.
+__device__ inline void ema_sweep(float* __restrict__ avg, const float* __restrict__ th, size_t n, float w) {
+  const size_t n4 = n >> 2, stride = (size_t)gridDim.x * kT;
+  float4* a4 = reinterpret_cast<float4*>(avg);
+  const float4* t4 = reinterpret_cast<const float4*>(th);
+  for (size_t q = (size_t)blockIdx.x * kT + threadIdx.x; q < n4; q += stride) {
+    float4 a = a4[q];
+    const float4 t = t4[q];
+    a.x = a.x - w * (a.x - t.x);
+    a.y = a.y - w * (a.y - t.y);
+    a.z = a.z - w * (a.z - t.z);
+    a.w = a.w - w * (a.w - t.w);
+    a4[q] = a;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const size_t e = (n4 << 2) + threadIdx.x;
+    const float a = avg[e];
+    avg[e] = a - w * (a - th[e]);
+  }
+}
+
+// Both segments of a network in one launch: the trainable buffer, then the (small) non-trainable state buffer; n2 == 0 touches
+// neither avg2 nor theta2.
+__global__ __launch_bounds__(kT) void ema_kernel(float* avg, const float* theta, size_t n, float* avg2, const float* theta2, size_t n2,
+                                                 float w) {
+  ema_sweep(avg, theta, n, w);
+  ema_sweep(avg2, theta2, n2, w);
+}
+
 bool al(const void* p) { return p == nullptr || bg::aligned16(p); }
 
 }  // namespace
@@ -150,6 +180,19 @@ int bg_adam_amsgrad_f32(float* theta, float* m, float* v, float* vhat, const flo
   bg::launch(adam_amsgrad_kernel, dim3(grid_for4(n)), dim3(kT), 0, L.s, theta, m, v, vhat, g, n, lr_t, b1, b2, eps);
   bg::bind_last(6, bg::BIND_F32_FROM_F64, slot);
   return L.done("adam_amsgrad_kernel");
+}
+
+int bg_ema_f32(float* avg, const float* theta, size_t n, float* avg2, const float* theta2, size_t n2, float w, void* stream) {
+  BG_REQUIRE(avg && theta && (n2 == 0 || (avg2 && theta2)), BG_ERR_NULL, "bg_ema_f32: null pointer");
+  BG_REQUIRE(n > 0, BG_ERR_BAD_SHAPE, "bg_ema_f32: empty tensor");
+  BG_REQUIRE(w >= 0.f && w <= 1.f, BG_ERR_BAD_SHAPE, "bg_ema_f32: w=%g outside [0, 1]", w);
+  BG_REQUIRE(al(avg) && al(theta) && (n2 == 0 || (al(avg2) && al(theta2))), BG_ERR_BAD_ALIGNMENT,
+             "bg_ema_f32: pointers must be 16-byte aligned");
+  bg::Launch L(stream, "ema", 0, 12.0 * (double)(n + n2));
+  const int slot = bg::take_bind(BG_BIND_EMA_W);           // step program: w re-read from a slot before every replay
+  bg::launch(ema_kernel, dim3(grid_for4(n)), dim3(kT), 0, L.s, avg, theta, n, n2 ? avg2 : nullptr, n2 ? theta2 : nullptr, n2, w);
+  bg::bind_last(6, bg::BIND_F32_FROM_F64, slot);
+  return L.done("ema_kernel");
 }
 
 }  // extern "C"

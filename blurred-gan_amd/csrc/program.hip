@@ -162,7 +162,8 @@ int bg_program_launches(const bg_program* p) { return p ? p->launches : 0; }
 
 int bg_program_bind_next(int what, int slot) {
   BG_REQUIRE(bg::t_rec, BG_ERR_UNSUPPORTED, "bg_program_bind_next: no program is being recorded on this thread");
-  BG_REQUIRE(what == BG_BIND_ADAM_LR || what == BG_BIND_RNG_OFFSET || what == BG_BIND_OPT_LR, BG_ERR_BAD_SHAPE, "bg_program_bind_next: what=%d", what);
+  BG_REQUIRE(what == BG_BIND_ADAM_LR || what == BG_BIND_RNG_OFFSET || what == BG_BIND_OPT_LR || what == BG_BIND_EMA_W, BG_ERR_BAD_SHAPE,
+             "bg_program_bind_next: what=%d", what);
   BG_REQUIRE(slot >= 0 && (size_t)slot + 1 < bg::t_rec->f64.size() + 0, BG_ERR_BAD_SHAPE, "bg_program_bind_next: slot %d out of range", slot);
   for (int i = 0; i < 4; ++i)
     if (bg::t_pending_slot[i] < 0) {

@@ -447,6 +447,16 @@ def adam_amsgrad(theta, m, v, vhat, g, lr_t, b1=0.9, b2=0.999, eps=1e-7):
           "bg_adam_amsgrad_f32")
 
 
+def ema(avg, theta, avg2, theta2, w):
+    """Weight averaging (tf.train.ExponentialMovingAverage): avg -= w * (avg - theta) over a network's trainable buffer and, in
+    the same launch, avg2 -= w * (avg2 - theta2) over its state buffer (both None: no second segment).  w = 1 - decay."""
+    assert avg.numel() == theta.numel() and (avg2 is None) == (theta2 is None)
+    n2 = 0 if avg2 is None else avg2.numel()
+    assert n2 == 0 or theta2.numel() == n2
+    check(_lib.load().bg_ema_f32(_ptr(avg), _ptr(theta), avg.numel(), _ptr(avg2) if n2 else None, _ptr(theta2) if n2 else None, n2, w,
+                                 _stream()), "bg_ema_f32")
+
+
 def _draw_offset(out, offset, counter):
     """Offset of a counter-based draw.  ``counter`` = (obj, attr): the draw starts at that host counter, which then advances by the
     Philox blocks the draw consumes; while a step program is being recorded the launch's offset is bound to the counter."""

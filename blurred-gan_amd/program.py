@@ -125,7 +125,8 @@ class Recorder:
     def bind_scalar(self, what, advance):
         """The next optimiser launch (BIND_ADAM_LR: bg_adam_f32's lr_t; BIND_OPT_LR: bg_sgd_f32 / bg_rmsprop_f32's lr,
         bg_adam_amsgrad_f32's lr_t) takes ``advance()``, the optimiser's scalar of its next iteration (which advances its
-        ``iterations``): a learning rate changed between steps, a schedule or a decay takes effect under replay."""
+        ``iterations``): a learning rate changed between steps, a schedule or a decay takes effect under replay.  BIND_EMA_W: the
+        next bg_ema_f32 launch takes the weight average's w of its next update the same way."""
         s = self._slot()
         _lib.check(self.lib.bg_program_bind_next(what, s), "bg_program_bind_next")
         f64 = self.f64

@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 import torch
 
-from . import dist, ops, optimizers, program
+from . import _lib, dist, ema as ema_mod, ops, optimizers, program
 from .gaussian_blur import Variable
 from .layers import Sequential, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
@@ -107,8 +107,9 @@ class WGAN:
                  config: TrainingConfig, *args, reproduce_vector_loss_quirk: bool = True, sync_metrics: bool = True,
                  sync_batchnorm: bool = True, merge_critic_passes: bool = True, gp_zero_norm_guard: bool = False,
                  merge_gp_filter_gradients: bool = True, step_replay: bool = True, persistent_input: bool = False,
-                 conv_math: str = "fp32", **kwargs):
+                 conv_math: str = "fp32", generator_ema=None, **kwargs):
         ops.conv_math_code(conv_math)        # ValueError before anything is built
+        ema_schedule = ema_mod.as_schedule(generator_ema)      # ValueError likewise
         self.hparams = hyperparams
         if dist.world_size() > 1 and int(hyperparams.global_batch_size) != int(hyperparams.batch_size) * dist.world_size():
             import warnings
@@ -170,6 +171,12 @@ class WGAN:
         self._rng_off = 0
         self._bufs = {}
         self._injected = None
+        # weight averaging (ema.py): None / a decay / a GeneratorEMA.  generator_ema is the averaged model -- the generator's
+        # structure in its own ParamStore, bit-copies of the live weights and BatchNorm statistics now -- and generator_step
+        # updates it with one launch after the optimizer; generate_samples(ema=True) runs it.  Off: nothing is allocated or launched
+        self.generator_ema_config = ema_schedule
+        self.generator_ema = None if ema_schedule is None else ema_mod.clone_structure(self.generator)
+        self.generator_ema_updates = 0
         self.conv_math = conv_math
 
     @property
@@ -185,6 +192,8 @@ class WGAN:
         self._conv_math = value
         self.generator.conv_math = value
         self.discriminator.conv_math = value
+        if self.generator_ema is not None:
+            self.generator_ema.conv_math = value
 
     # ------------------------------------------------------------------ small helpers
     @property
@@ -308,11 +317,17 @@ class WGAN:
         """Everything that shapes the launch list of a step or is baked into its kernel arguments."""
         G, D = self.generator.net(), self.discriminator.net()
         hp = tuple(sorted((k, _plain(v)) for k, v in vars(self.hparams).items() if isinstance(v, (numbers.Number, np.generic, str, bool))))
-        return (kind, tuple(reals.shape), reals.data_ptr(), D.blur_n_taps(), G.store.tr_dirty, D.store.tr_dirty, self.merge_critic_passes,
-                self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
-                self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
-                G.store.n_train, D.store.n_train, G.conv_math, D.conv_math, _env_switches(), hp,
-                self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
+        key = (kind, tuple(reals.shape), reals.data_ptr(), D.blur_n_taps(), G.store.tr_dirty, D.store.tr_dirty, self.merge_critic_passes,
+               self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
+               self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
+               G.store.n_train, D.store.n_train, G.conv_math, D.conv_math, _env_switches(), hp,
+               self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
+        if self.generator_ema is not None:
+            # the averaged model's presence, the two buffers the update writes and the schedule's static configuration: a program
+            # recorded without the average, or on other buffers, never replays
+            E = self.generator_ema.store
+            key += (("generator_ema", E.theta.data_ptr(), E.state.data_ptr(), self.generator_ema_config.static_config()),)
+        return key
 
     @staticmethod
     def _optimizer_key(model):
@@ -323,7 +338,11 @@ class WGAN:
 
     def _exit_state(self):
         G, D = self.generator.net(), self.discriminator.net()
-        return [(G.store, "tr_dirty", G.store.tr_dirty), (D.store, "tr_dirty", D.store.tr_dirty)]
+        state = [(G.store, "tr_dirty", G.store.tr_dirty), (D.store, "tr_dirty", D.store.tr_dirty)]
+        if self.generator_ema is not None:
+            E = self.generator_ema.store
+            state.append((E, "tr_dirty", E.tr_dirty))
+        return state
 
     def _metrics_dev(self):
         return self._buf("step_metrics", (16,))
@@ -360,13 +379,19 @@ class WGAN:
         assert self.batch_size is not None
         return self._uniform("latents", (self.batch_size, self.latent_size))
 
-    def generate_samples(self, latents=None, training=False):
+    def generate_samples(self, latents=None, training=False, ema=False):
+        """``ema=True``: the averaged generator (``generator_ema=`` of the constructor), inference BatchNorm on its own averaged
+        moving statistics."""
+        if ema and self.generator_ema is None:
+            raise ValueError("generate_samples(ema=True): this model has no averaged generator (construct it with generator_ema=...)")
+        if ema and training:
+            raise ValueError("generate_samples(ema=True) runs inference BatchNorm: training=True would overwrite the averaged statistics")
         if latents is None:
             if self.batch_size is None:
                 self.batch_size = self.hparams.batch_size
             latents = self.latents_batch()
         latents = self._as_device(latents)
-        G = self.generator.net()
+        G = (self.generator_ema if ema else self.generator).net()
         ctx = G.context(int(latents.shape[0]), "g")
         return G.forward(ctx, latents, training=training)
 
@@ -513,11 +538,41 @@ class WGAN:
         G.backward(cg, dfakes, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=red)
         red.finish()
         optimizers.get_optimizer(self.generator).apply(store)
+        if self.generator_ema is not None:
+            self._update_generator_ema()
         if self.sync_metrics and not self._defer_metrics:
             m = self._read_metrics()
             self._record_g_metrics(m[8:12])
             return m[1 + 8]
         return None
+
+    # ---- weight averaging (ema.py)
+    def _advance_generator_ema(self):
+        """w = 1 - beta of the next update of the average, in double; advances ``generator_ema_updates``."""
+        w = self.generator_ema_config.w_at(self.generator_ema_updates, self.batch_size, dist.world_size(), self.d_steps_per_g_step)
+        self.generator_ema_updates += 1
+        return w
+
+    def _update_generator_ema(self):
+        """avg -= w * (avg - theta) over the generator's trainable buffer and its BatchNorm moving statistics: one launch
+        (bg_ema_f32).  Every data-parallel rank applies the same update to identical inputs, so nothing is communicated."""
+        G, E = self.generator.store, self.generator_ema.store
+        rec = program.active()
+        if rec is not None:                 # step program: the recorded launch takes w of the NEXT update from a slot
+            rec.bind_scalar(_lib.BIND_EMA_W, self._advance_generator_ema)
+        n, n2 = G.n_train, G.n_state
+        ops.ema(E.theta[:n], G.theta[:n], E.state[:n2] if n2 else None, G.state[:n2] if n2 else None, self._advance_generator_ema())
+        E.tr_dirty = True                   # the transposed kernel copies are refreshed by the averaged model's next forward
+
+    def reset_generator_ema(self):
+        """averages <- live weights, update count <- 0 (after ``set_weights`` / ``load_weights`` on the live generator)."""
+        if self.generator_ema is None:
+            raise ValueError("reset_generator_ema: this model has no averaged generator (construct it with generator_ema=...)")
+        G, E = self.generator.store, self.generator_ema.store
+        E.theta.copy_(G.theta)
+        E.state.copy_(G.state)
+        E.tr_dirty = True
+        self.generator_ema_updates = 0
 
     # ---- bookkeeping / Keras surface
     def log_image_summaries(self):
@@ -548,6 +603,8 @@ class WGAN:
         """wgan.py:229-231."""
         self.discriminator.save_weights(filepath + "_discriminator", overwrite, save_format)
         self.generator.save_weights(filepath + "_generator", overwrite, save_format)
+        if self.generator_ema is not None:
+            self.generator_ema.save_weights(filepath + "_generator_ema", overwrite, save_format)
 
     def fit(self, x, y=None, epochs=1, initial_epoch=0, callbacks=None, steps_per_epoch=None, verbose=0):
         """The slice of ``tf.keras.Model.fit`` the reference demos rely on (demo_mnist.py:187-206): iterate

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 import blurred_gan_amd as blurred_gan
-from blurred_gan_amd import BlurredWGANGP, TrainingConfig, callbacks, layers, utils
+from blurred_gan_amd import BlurredWGANGP, GeneratorEMA, TrainingConfig, callbacks, layers, utils
 from blurred_gan_amd.checkpoint import CheckpointManager
 
 
@@ -71,6 +71,11 @@ def main(argv=None):
     parser.add_argument("--results_dir", default="results")
     parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
                         help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
+    ema_group = parser.add_mutually_exclusive_group()
+    ema_group.add_argument("--g-ema-decay", dest="g_ema_decay", type=float, default=None,
+                           help="average the generator's weights with this decay per generator update (off by default)")
+    ema_group.add_argument("--g-ema-halflife-images", dest="g_ema_halflife_images", type=float, default=None,
+                           help="average the generator's weights with a half-life of this many images (off by default)")
     args = parser.parse_args(argv)
     hyperparameters = BlurredWGANGP.HyperParameters.from_args(args)
     config = TrainingConfig.from_args(args)
@@ -85,7 +90,13 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
     gen, disc = DCGANGenerator(), DCGANDiscriminator()
-    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math)
+    generator_ema = None
+    if args.g_ema_decay is not None:
+        generator_ema = GeneratorEMA(decay=args.g_ema_decay)
+    elif args.g_ema_halflife_images is not None:
+        generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
+    gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
+                                    generator_ema=generator_ema)
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)

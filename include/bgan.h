@@ -310,6 +310,15 @@ int bg_rmsprop_f32(float* theta, float* r, float* p, float* mg, const float* g, 
 int bg_adam_amsgrad_f32(float* theta, float* m, float* v, float* vhat, const float* g, size_t n, float lr_t, float b1, float b2,
                         float eps, void* stream);
 
+/* ---- weight averaging: tf.train.ExponentialMovingAverage over a network (the averaged generator GANs sample from) ----
+ * TF's assign_moving_average, per element in fp32 and in this order: avg = avg - w * (avg - theta), with w = 1 - decay formed by
+ * the host in double and rounded once (1 - 0.999f in fp32 is 1.00004673e-3).  Two segments in ONE launch: a network's flat
+ * trainable buffer (avg, theta, n) and its non-trainable state buffer, the BatchNorm moving statistics (avg2, theta2, n2;
+ * n2 == 0: both may be NULL).  16-byte aligned pointers (BG_ERR_BAD_ALIGNMENT otherwise), any n > 0 and n2 (scalar tails cover
+ * n % 4), w in [0, 1].  The average is plain fp32, as TF's: for w below about 1e-4 an update can fall under one ulp of the
+ * average and is then lost to rounding.  Under a step program w is bound with BG_BIND_EMA_W. */
+int bg_ema_f32(float* avg, const float* theta, size_t n, float* avg2, const float* theta2, size_t n2, float w, void* stream);
+
 /* ---- RNG: tf.random.uniform (wgan.py:118,237) and Dropout masks; counter-based, own stream ---- */
 int bg_uniform_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint64_t offset, void* stream);
@@ -322,9 +331,9 @@ int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint
  * While recording, every kernel launch of the calling thread is executed AND appended to `p` as (kernel, grid, block, LDS bytes,
  * a by-value copy of every kernel argument).  bg_program_replay(p, first, last, stream) issues nodes [first, last) (last < 0 =
  * all) on `stream` -- no geometry checks, tap tables, grid planning or host language in between.  What changes per step:
- *   - the optimisers' learning rates and the RNG counter offsets: announce bg_program_bind_next(what, slot) right before the call
- *     that owns the argument; the recorded launch then re-reads slots_f64[slot] (BG_BIND_ADAM_LR, BG_BIND_OPT_LR) /
- *     slots_u64[slot] (BG_BIND_RNG_OFFSET) before every replay.  The slot arrays belong to the program and are written directly by the host.
+ *   - the optimisers' learning rates, the weight average's w and the RNG counter offsets: announce bg_program_bind_next(what, slot)
+ *     right before the call that owns the argument; the recorded launch then re-reads slots_f64[slot] (BG_BIND_ADAM_LR,
+ *     BG_BIND_OPT_LR, BG_BIND_EMA_W) / slots_u64[slot] (BG_BIND_RNG_OFFSET) before every replay.  The slot arrays belong to the program and are written directly by the host.
  *   - the blur taps' VALUES live in a caller-owned device buffer the host refreshes in stream order; a changed tap COUNT selects
  *     other kernels and needs a newly recorded program (the host keeps one per count).
  *   - collectives (data parallel) are the host's: it splits the replay at the node indices bg_program_size() returned when the
@@ -344,6 +353,7 @@ typedef struct bg_program bg_program;
 #define BG_BIND_ADAM_LR 1     /* bg_adam_f32: lr_t <- (float) slots_f64[slot]                         */
 #define BG_BIND_RNG_OFFSET 2  /* bg_uniform_f32, bg_keep_mask_u8: offset <- slots_u64[slot]            */
 #define BG_BIND_OPT_LR 3      /* bg_sgd_f32, bg_rmsprop_f32: lr, bg_adam_amsgrad_f32: lr_t <- (float) slots_f64[slot] */
+#define BG_BIND_EMA_W 4       /* bg_ema_f32: w <- (float) slots_f64[slot]                              */
 int bg_program_create(bg_program** out, int n_slots);
 int bg_program_destroy(bg_program* p);
 int bg_program_record_begin(bg_program* p);
