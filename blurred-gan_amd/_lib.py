@@ -86,6 +86,7 @@ SIGNATURES = {
     "bg_wgangp_d_loss": (_i, [_p, _p, _p, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
     "bg_wgan_g_loss": (_i, [_p, _i, _f, _p, _p, _p]),
     "bg_u8_normalize_resize_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "bg_u8_gather_normalize_resize_f32": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bg_adam_f32": (_i, [_p, _p, _p, _p, _z, _f, _f, _f, _f, _p]),
     "bg_sgd_f32": (_i, [_p, _p, _p, _z, _f, _f, _i, _p]),
     "bg_rmsprop_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _i, _p]),

@@ -423,6 +423,20 @@ def u8_normalize_resize(src_u8, dst):
     return dst
 
 
+def u8_gather_normalize_resize(src_u8, idx, dst, flip=None):
+    """dst[b] = resize(normalise(src_u8[idx[b]])), mirrored left-right where flip[b] != 0, in ONE launch: src_u8 is the
+    device-resident uint8 [N,Hs,Ws,C] dataset, idx an int32 device vector of dst.shape[0] entries (repeats / any order), flip an
+    optional uint8 one.  The kernel cannot check idx: the caller guarantees every entry lies in [0, N)."""
+    assert src_u8.dtype == torch.uint8 and dst.dtype == torch.float32 and idx.dtype == torch.int32
+    assert flip is None or flip.dtype == torch.uint8
+    N, Hs, Ws, Cc = src_u8.shape
+    B = dst.shape[0]
+    assert dst.dim() == 4 and dst.shape[3] == Cc and idx.numel() == B and (flip is None or flip.numel() == B)
+    check(_lib.load().bg_u8_gather_normalize_resize_f32(_ptr(src_u8), N, _ptr(idx), _ptr(flip), _ptr(dst), B, Hs, Ws, Cc, dst.shape[1],
+                                                        dst.shape[2], _stream()), "bg_u8_gather_normalize_resize_f32")
+    return dst
+
+
 def adam(theta, m, v, g, lr_t, b1=0.9, b2=0.999, eps=1e-7):
     assert theta.numel() == m.numel() == v.numel() == g.numel()
     check(_lib.load().bg_adam_f32(_ptr(theta), _ptr(m), _ptr(v), _ptr(g), theta.numel(), lr_t, b1, b2, eps, _stream()), "bg_adam_f32")

@@ -1,5 +1,8 @@
 """Counterpart of reference demo_celeba.py (128x128 CelebA stack, demo_celeba.py:51-124), on the HIP kernels.
-Dataset: `$DATASETS_DIR/celeba_128.npy` (float32 [N,128,128,3] in [-1,1]) when present, else synthetic batches."""
+Dataset: `$DATASETS_DIR/celeba_128.npy` (float32 [N,128,128,3] in [-1,1]) when present, else synthetic batches.
+`--dataset PATH` (a uint8 [N,H,W,3] .npy, e.g. CelebA at its native 218x178) trains from a device-resident `DeviceDataset` instead:
+the file goes to the GPU once, every epoch is reshuffled, ranks read disjoint shards, and one launch per batch normalises, resizes
+to 128x128 and (`--flip`) mirrors."""
 import argparse
 import os
 
@@ -7,7 +10,7 @@ import numpy as np
 import torch
 
 import blurred_gan_amd as blurred_gan
-from blurred_gan_amd import BlurredWGANGP, GeneratorEMA, TrainingConfig, callbacks, layers, utils
+from blurred_gan_amd import BlurredWGANGP, DeviceDataset, GeneratorEMA, TrainingConfig, callbacks, layers, utils
 from blurred_gan_amd.checkpoint import CheckpointManager
 
 
@@ -71,6 +74,9 @@ def main(argv=None):
     parser.add_argument("--results_dir", default="results")
     parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
                         help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
+    parser.add_argument("--dataset", default=None, metavar="PATH",
+                        help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
+    parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
     ema_group = parser.add_mutually_exclusive_group()
     ema_group.add_argument("--g-ema-decay", dest="g_ema_decay", type=float, default=None,
                            help="average the generator's weights with this decay per generator update (off by default)")
@@ -85,8 +91,13 @@ def main(argv=None):
     if rank0:
         print("Num gpus:", num_gpus)
     hyperparameters.global_batch_size = hyperparameters.batch_size * num_gpus
-    dataset = make_dataset(hyperparameters.batch_size, n_batches=args.max_batches, seed=dist.rank())
-    total_n_examples = 202_599
+    if args.dataset:
+        # sharded by rank, reshuffled every epoch; the ring buffers keep their addresses, so the step programs read them in place
+        dataset = DeviceDataset(args.dataset, image_size=(128, 128), batch_size=hyperparameters.batch_size, flip=args.flip, seed=123123)
+        total_n_examples = dataset.samples_per_epoch
+    else:
+        dataset = make_dataset(hyperparameters.batch_size, n_batches=args.max_batches, seed=dist.rank())
+        total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
     gen, disc = DCGANGenerator(), DCGANDiscriminator()
@@ -96,7 +107,7 @@ def main(argv=None):
     elif args.g_ema_halflife_images is not None:
         generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
     gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
-                                    generator_ema=generator_ema)
+                                    generator_ema=generator_ema, persistent_input=bool(args.dataset))
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)
@@ -107,7 +118,11 @@ def main(argv=None):
         cbs = [callbacks.GenerateSampleGridCallback(log_dir=config.log_dir, every_n_examples=5_000), *cbs,
                callbacks.SaveModelCallback(manager, n=10_000), callbacks.LogMetricsCallback()]
     try:
-        gan.fit(x=dataset, y=None, epochs=args.epochs, initial_epoch=gan.n_img // total_n_examples, callbacks=cbs)
+        initial_epoch = gan.n_img // total_n_examples
+        if args.dataset:
+            dataset.epoch = int(initial_epoch)          # a resumed run goes on with the epoch's own order
+        gan.fit(x=dataset, y=None, epochs=args.epochs, initial_epoch=initial_epoch, callbacks=cbs,
+                steps_per_epoch=args.max_batches if args.dataset else None)
     except KeyboardInterrupt:
         if rank0:
             manager.save()

@@ -286,6 +286,16 @@ int bg_wgan_g_loss(const float* s, int B, float inv_gbs, float* ds, float* metri
  *      tf.image.resize(bilinear, half-pixel centres) to [Hd, Wd] (normalise BEFORE resize, aspect not preserved).
  *      Hd == Hs && Wd == Ws is the MNIST pipeline (normalise only). */
 int bg_u8_normalize_resize_f32(const uint8_t* src, float* dst, int B, int Hs, int Ws, int C, int Hd, int Wd, void* stream);
+/* The same pipeline fed from a DEVICE-RESIDENT uint8 dataset src[N, Hs, Ws, C] in ONE launch (the tfds ... map ... shuffle ... batch
+ * chain of demo_celeba.py:15-48 with the whole dataset in HBM): dst[b] = resize(normalise(src[idx_d[b]])), b < B, with the arithmetic
+ * of bg_u8_normalize_resize_f32, bit for bit.  idx_d[B] (device, int32) may repeat and come in any order; image byte offsets are
+ * formed in 64 bits.  flip_d[B] (device, uint8; may be NULL = no mirroring): where flip_d[b] != 0 the sample is mirrored left-right
+ * at the OUTPUT index, dst[b, y, x, c] = unmirrored[b, y, Wd-1-x, c], so a mirrored sample is bit-identical to the mirror of the
+ * unmirrored one.  dst must be 16-byte aligned (BG_ERR_BAD_ALIGNMENT, nothing launched): C = 1, 3, 4 write 16-byte stores with a
+ * scalar tail of (B*Hd*Wd) % 4 pixels.  The library cannot see device memory: EVERY idx_d[b] MUST lie in [0, N) -- the caller
+ * guarantees it.  Takes no step-program binding; it is meant to run between steps, outside any recorded program. */
+int bg_u8_gather_normalize_resize_f32(const uint8_t* src, int N, const int32_t* idx_d, const uint8_t* flip_d /* may be NULL */,
+                                      float* dst, int B, int Hs, int Ws, int C, int Hd, int Wd, void* stream);
 
 /* ---- optimiser: tf.keras.optimizers.Adam (wgan.py:56-61,141,167) ----------------------------- */
 /* lr_t = lr*sqrt(1-b2^t)/(1-b1^t) is computed by the caller (host) per step. */
