@@ -87,6 +87,15 @@ SIGNATURES = {
     "bg_wgan_g_loss": (_i, [_p, _i, _f, _p, _p, _p]),
     "bg_u8_normalize_resize_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bg_u8_gather_normalize_resize_f32": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "bg_swd_ingest_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "bg_pyr_down_f32": (_i, [_p, _p, _i, _i, _i, _p]),
+    "bg_pyr_up_f32": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "bg_swd_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "bg_swd_standardize_workspace_bytes": (_z, [_i, _i]),
+    "bg_swd_standardize_f32": (_i, [_p, _i, _i, _p, _p, _z, _p]),
+    "bg_sort_rows_f32": (_i, [_p, _i, _i, _p]),
+    "bg_abs_diff_mean_workspace_bytes": (_z, [_z, _i]),
+    "bg_abs_diff_mean_f32": (_i, [_p, _p, _z, _i, _p, _p, _z, _p]),
     "bg_adam_f32": (_i, [_p, _p, _p, _p, _z, _f, _f, _f, _f, _p]),
     "bg_sgd_f32": (_i, [_p, _p, _p, _z, _f, _f, _i, _p]),
     "bg_rmsprop_f32": (_i, [_p, _p, _p, _p, _p, _z, _f, _f, _f, _f, _i, _p]),

@@ -241,14 +241,28 @@ class FeedImagesToMetricCallback(ExecuteEveryNExamplesCallback):
             w.scalar(self.metric.name, result, step=int(self.model.n_img))
 
 
+def _identity(images):
+    return images
+
+
 class SWDMetricCallback(FeedImagesToMetricCallback):
     """callbacks.py:186-198 (the reference's ``write_result`` reads an undefined ``self.swd_metric``; fixed)."""
 
-    def __init__(self, image_preprocessing_fn, num_samples=1000, every_n_examples=10_000, seed=None, on_device=False):
-        """``on_device``: the preprocessed minibatches (device tensors) are not copied to the host; the metric's device path runs."""
+    def __init__(self, image_preprocessing_fn, num_samples=1000, every_n_examples=10_000, seed=None, on_device=False, native=False):
+        """``on_device``: the preprocessed minibatches (device tensors) are not copied to the host; the metric's device path runs.
+        ``native``: the library's SWD kernels (metrics.SWDMetric(native=True)).  ``image_preprocessing_fn`` may then be ``None``:
+        the metric takes ``model.images`` as they are -- NHWC in [-1, 1], 1 or 3 channels -- to 0..255 planar RGB in one launch
+        (x * 127.5 + 127.5, the demos' preprocessing, demo_mnist.py:180-184).  A callable that is given is applied first and
+        must return NCHW 0..255 minibatches as for the other paths."""
         from .metrics import SWDMetric
-        super().__init__(SWDMetric(seed=seed, on_device=on_device), image_preprocessing_fn, num_samples=num_samples,
-                         every_n_examples=every_n_examples)
+        if image_preprocessing_fn is None:
+            if not native:
+                raise ValueError("SWDMetricCallback: image_preprocessing_fn=None needs native=True")
+            metric = SWDMetric(seed=seed, native=True, data_format="NHWC", scale=127.5, shift=127.5)
+            image_preprocessing_fn = _identity
+        else:
+            metric = SWDMetric(seed=seed, on_device=on_device, native=native)
+        super().__init__(metric, image_preprocessing_fn, num_samples=num_samples, every_n_examples=every_n_examples)
 
     def write_result(self):
         results = self.metric.results()

@@ -437,6 +437,85 @@ def u8_gather_normalize_resize(src_u8, idx, dst, flip=None):
     return dst
 
 
+# ------------------------------------------------------------------ SWD metric (include/bgan.h "SWD metric")
+def swd_ingest(src, dst, nhwc, scale=1.0, shift=0.0):
+    """dst[B,3,H,W] = src * scale + shift from an NHWC (``nhwc``) or NCHW float32 batch of 1 or 3 channels; one channel is
+    replicated three times."""
+    _f32(src, dst)
+    assert src.dim() == 4 and dst.dim() == 4
+    B, H, W, Cc = src.shape if nhwc else (src.shape[0], src.shape[2], src.shape[3], src.shape[1])
+    assert tuple(dst.shape) == (B, 3, H, W)
+    check(_lib.load().bg_swd_ingest_f32(_ptr(src), _ptr(dst), B, H, W, Cc, int(bool(nhwc)), scale, shift, _stream()), "bg_swd_ingest_f32")
+    return dst
+
+
+def pyr_down(x, y):
+    """y[..., ceil(H/2), ceil(W/2)] = pyr_down(x[..., H, W]): the host sliced_wasserstein.pyr_down bit for bit."""
+    _f32(x, y)
+    H, W = x.shape[-2:]
+    planes = x.numel() // (H * W)
+    assert y.numel() == planes * ((H + 1) // 2) * ((W + 1) // 2)
+    check(_lib.load().bg_pyr_down_f32(_ptr(x), _ptr(y), planes, H, W, _stream()), "bg_pyr_down_f32")
+    return y
+
+
+def pyr_up(low, out, minuend=None):
+    """out[..., 2h, 2w] = pyr_up(low[..., h, w]), or minuend - pyr_up(low) (``minuend`` may be ``out``)."""
+    _f32(low, out, minuend)
+    h, w = low.shape[-2:]
+    planes = low.numel() // (h * w)
+    assert out.numel() == 4 * low.numel() and (minuend is None or minuend.numel() == out.numel())
+    check(_lib.load().bg_pyr_up_f32(_ptr(low), _ptr(minuend), _ptr(out), planes, h, w, _stream()), "bg_pyr_up_f32")
+    return out
+
+
+def swd_gather(level, cx, cy, desc, nhood, per_image):
+    """desc[t, c, a, b] = level[t // per_image, c, cy[t] + b - half, cx[t] + a - half]; cx, cy: int32 device vectors whose
+    entries the caller has checked to lie in [half, size - half)."""
+    _f32(level, desc)
+    assert cx.dtype == torch.int32 and cy.dtype == torch.int32
+    B, Cc, H, W = level.shape
+    total = B * per_image
+    assert Cc == 3 and cx.numel() == total == cy.numel() and desc.numel() == total * 3 * nhood * nhood
+    check(_lib.load().bg_swd_gather_f32(_ptr(level), _ptr(cx), _ptr(cy), _ptr(desc), B, H, W, nhood, per_image, _stream()),
+          "bg_swd_gather_f32")
+    return desc
+
+
+def swd_standardize_workspace_bytes(rows, nhood):
+    return _lib.load().bg_swd_standardize_workspace_bytes(rows, nhood)
+
+
+def swd_standardize(desc, rows, nhood, ws, stats=None):
+    """desc[rows, 3, nhood, nhood] <- (desc - mean) / std per channel, in place; float64 statistics (``stats``: 6 doubles)."""
+    _f32(desc)
+    assert desc.numel() == rows * 3 * nhood * nhood and (stats is None or (stats.dtype == torch.float64 and stats.numel() == 6))
+    check(_lib.load().bg_swd_standardize_f32(_ptr(desc), rows, nhood, _ptr(stats), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+          "bg_swd_standardize_f32")
+    return desc
+
+
+def sort_rows(x, rows, n):
+    """Sorts each of the ``rows`` contiguous rows of ``n`` floats ascending, in place."""
+    _f32(x)
+    assert x.numel() == rows * n
+    check(_lib.load().bg_sort_rows_f32(_ptr(x), rows, n, _stream()), "bg_sort_rows_f32")
+    return x
+
+
+def abs_diff_mean_workspace_bytes(seg, nseg):
+    return _lib.load().bg_abs_diff_mean_workspace_bytes(seg, nseg)
+
+
+def abs_diff_mean(a, b, seg, nseg, out, ws):
+    """out[s] (float64) = mean |a - b| over segment s of ``seg`` elements."""
+    _f32(a, b)
+    assert a.numel() == seg * nseg == b.numel() and out.dtype == torch.float64 and out.numel() == nseg
+    check(_lib.load().bg_abs_diff_mean_f32(_ptr(a), _ptr(b), seg, nseg, _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+          "bg_abs_diff_mean_f32")
+    return out
+
+
 def adam(theta, m, v, g, lr_t, b1=0.9, b2=0.999, eps=1e-7):
     assert theta.numel() == m.numel() == v.numel() == g.numel()
     check(_lib.load().bg_adam_f32(_ptr(theta), _ptr(m), _ptr(v), _ptr(g), theta.numel(), lr_t, b1, b2, eps, _stream()), "bg_adam_f32")

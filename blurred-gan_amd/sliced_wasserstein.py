@@ -145,7 +145,9 @@ def sliced_wasserstein(A, B, dir_repeats, dirs_per_repeat, rng):
 class API:
     """Same driver protocol as the reference's ``API`` (begin / feed / end), RNG explicit."""
 
-    def __init__(self, image_shape, seed=None):
+    def __init__(self, image_shape, seed=None, native=False):
+        """``native``: minibatches are float32 NCHW tensors on the GPU and the library's kernels (swd_native.py) do the work."""
+        self.native = native
         self.nhood_size, self.nhoods_per_image, self.dir_repeats, self.dirs_per_repeat = 7, 128, 4, 128
         self.resolutions = []
         res = image_shape[1]
@@ -162,10 +164,23 @@ class API:
         self.descriptors = [[] for _ in self.resolutions]
 
     def feed(self, mode, minibatch):
+        if self.native:
+            from . import swd_native as sn
+            for lod, level in enumerate(sn.generate_laplacian_pyramid(minibatch, len(self.resolutions))):
+                self.descriptors[lod].append(sn.get_descriptors_for_minibatch(level, self.nhood_size, self.nhoods_per_image, self.rng))
+            return
         for lod, level in enumerate(generate_laplacian_pyramid(minibatch, len(self.resolutions))):
             self.descriptors[lod].append(get_descriptors_for_minibatch(level, self.nhood_size, self.nhoods_per_image, self.rng))
 
     def end(self, mode):
+        if self.native:
+            from . import swd_native as sn
+            desc = [sn.finalize_descriptors(d) for d in self.descriptors]
+            del self.descriptors
+            if mode in ("warmup", "reals"):
+                self.desc_real = desc
+            dist = [d * 1e3 for d in sn.level_distances(self.desc_real, desc, self.dir_repeats, self.dirs_per_repeat, self.rng)]
+            return dist + [float(np.mean(dist))]
         desc = [finalize_descriptors(d) for d in self.descriptors]
         del self.descriptors
         if mode in ("warmup", "reals"):

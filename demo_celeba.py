@@ -62,10 +62,8 @@ class DCGANDiscriminator(layers.Sequential):
         self.add(layers.Dense(1, activation="linear"))
 
 
-def main(argv=None):
-    """demo_celeba.py:127-246; multi-GPU decisions as in demo_mnist.main (global batch = per-GPU batch x replicas, one run
-    directory made by rank 0, file-writing callbacks on rank 0 only)."""
-    blurred_gan.set_seed(123123)
+def make_parser():
+    """The demo's command line."""
     parser = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     BlurredWGANGP.HyperParameters.add_arguments(parser)
     TrainingConfig.add_arguments(parser)
@@ -82,6 +80,19 @@ def main(argv=None):
                            help="average the generator's weights with this decay per generator update (off by default)")
     ema_group.add_argument("--g-ema-halflife-images", dest="g_ema_halflife_images", type=float, default=None,
                            help="average the generator's weights with a half-life of this many images (off by default)")
+    parser.add_argument("--swd-every-n-examples", dest="swd_every_n_examples", type=int, default=0, metavar="N",
+                        help="measure the sliced Wasserstein distance between reals and fakes every N training examples on the "
+                             "library's SWD kernels (0: off; the reference demo measures every 50000)")
+    parser.add_argument("--swd-samples", dest="swd_samples", type=int, default=1000,
+                        help="images per set of one SWD measurement")
+    return parser
+
+
+def main(argv=None):
+    """demo_celeba.py:127-246; multi-GPU decisions as in demo_mnist.main (global batch = per-GPU batch x replicas, one run
+    directory made by rank 0, file-writing callbacks on rank 0 only)."""
+    blurred_gan.set_seed(123123)
+    parser = make_parser()
     args = parser.parse_args(argv)
     hyperparameters = BlurredWGANGP.HyperParameters.from_args(args)
     config = TrainingConfig.from_args(args)
@@ -117,6 +128,9 @@ def main(argv=None):
         gan.config.save_json(os.path.join(config.log_dir, "train_config.json"))
         cbs = [callbacks.GenerateSampleGridCallback(log_dir=config.log_dir, every_n_examples=5_000), *cbs,
                callbacks.SaveModelCallback(manager, n=10_000), callbacks.LogMetricsCallback()]
+        if args.swd_every_n_examples > 0:        # the reference's SWDMetricCallback, fed from model.images with no host work
+            cbs.append(callbacks.SWDMetricCallback(None, num_samples=args.swd_samples, every_n_examples=args.swd_every_n_examples,
+                                                   native=True, seed=123123))
     try:
         initial_epoch = gan.n_img // total_n_examples
         if args.dataset:

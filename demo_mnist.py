@@ -66,12 +66,8 @@ class DCGANDiscriminator(layers.Sequential):
         self.add(layers.Dense(1))
 
 
-def main(argv=None):
-    """demo_mnist.py:91-219.  Under ``torchrun`` (one process per GPU) every rank trains on its own shard; what the reference
-    leaves undone for multi-GPU (demo_mnist.py:116 "TODO") is decided here: ``global_batch_size`` = per-GPU batch x replicas
-    (wgan.py:130,157 scale the losses by it), ONE run directory created by rank 0 and shared, and the host-side callbacks that
-    write files (checkpoints, sample grids, scalar logs) on rank 0 only."""
-    blurred_gan.set_seed(123123)
+def make_parser():
+    """The demo's command line."""
     parser = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     BlurredWGANGP.HyperParameters.add_arguments(parser)
     TrainingConfig.add_arguments(parser)
@@ -88,6 +84,21 @@ def main(argv=None):
                            help="average the generator's weights with this decay per generator update (off by default)")
     ema_group.add_argument("--g-ema-halflife-images", dest="g_ema_halflife_images", type=float, default=None,
                            help="average the generator's weights with a half-life of this many images (off by default)")
+    parser.add_argument("--swd-every-n-examples", dest="swd_every_n_examples", type=int, default=0, metavar="N",
+                        help="measure the sliced Wasserstein distance between reals and fakes every N training examples on the "
+                             "library's SWD kernels (0: off; the reference demo measures every 50000)")
+    parser.add_argument("--swd-samples", dest="swd_samples", type=int, default=1000,
+                        help="images per set of one SWD measurement")
+    return parser
+
+
+def main(argv=None):
+    """demo_mnist.py:91-219.  Under ``torchrun`` (one process per GPU) every rank trains on its own shard; what the reference
+    leaves undone for multi-GPU (demo_mnist.py:116 "TODO") is decided here: ``global_batch_size`` = per-GPU batch x replicas
+    (wgan.py:130,157 scale the losses by it), ONE run directory created by rank 0 and shared, and the host-side callbacks that
+    write files (checkpoints, sample grids, scalar logs) on rank 0 only."""
+    blurred_gan.set_seed(123123)
+    parser = make_parser()
     args = parser.parse_args(argv)
     hyperparameters = BlurredWGANGP.HyperParameters.from_args(args)
     config = TrainingConfig.from_args(args)
@@ -131,6 +142,9 @@ def main(argv=None):
         gan.config.save_json(os.path.join(config.log_dir, "train_config.json"))
         cbs = [callbacks.GenerateSampleGridCallback(log_dir=config.log_dir, every_n_examples=5_000), *cbs,
                callbacks.SaveModelCallback(manager, n=10_000), callbacks.LogMetricsCallback()]
+        if args.swd_every_n_examples > 0:        # the reference's SWDMetricCallback, fed from model.images with no host work
+            cbs.append(callbacks.SWDMetricCallback(None, num_samples=args.swd_samples, every_n_examples=args.swd_every_n_examples,
+                                                   native=True, seed=123123))
     try:
         initial_epoch = gan.n_img // total_n_examples
         if args.dataset:

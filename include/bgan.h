@@ -297,6 +297,48 @@ int bg_u8_normalize_resize_f32(const uint8_t* src, float* dst, int B, int Hs, in
 int bg_u8_gather_normalize_resize_f32(const uint8_t* src, int N, const int32_t* idx_d, const uint8_t* flip_d /* may be NULL */,
                                       float* dst, int B, int Hs, int Ws, int C, int Hd, int Wd, void* stream);
 
+/* ---- SWD metric: sliced Wasserstein distance between image sets (sliced_wasserstein.py:13-51,72-88; metrics.py:93-157) ----
+ * The evaluation the reference's SWDMetricCallback runs inside the training loop, as kernels over float32 planar NCHW buffers.
+ * The random DRAWS (patch centres, directions) stay on the host; the projection between standardize and sort is bg_gemm_f32
+ * (P[dirs, rows] = dirs^T * desc^T, transA = transB = 1: each direction's projections are one contiguous row).  Every entry
+ * moves 16 bytes per lane where the geometry keeps the addresses 16-byte aligned and one float per lane otherwise; pointers
+ * must be 4-byte (doubles: 8-byte) aligned (BG_ERR_BAD_ALIGNMENT).  A refused call launches nothing.  None of the entries takes
+ * a step-program binding: they run between steps, outside any recorded program.  Buffers hold fewer than 2^31 elements. */
+/* dst[B,3,H,W] = src * scale + shift (two fp32 roundings), src NHWC (src_nhwc != 0) or NCHW with C = 1 or 3 channels
+ * (BG_ERR_BAD_SHAPE otherwise); C = 1 is replicated three times (tf.image.grayscale_to_rgb).  model.images ([-1, 1], NHWC) enter
+ * the metric through this call with scale = shift = 127.5 and no transpose (demo_mnist.py:180-184). */
+int bg_swd_ingest_f32(const float* src, float* dst, int B, int H, int W, int C, int src_nhwc, float scale, float shift, void* stream);
+/* sliced_wasserstein.py:65-74 (pyr_down): y[planes, ceil(H/2), ceil(W/2)] = every second pixel of the separable 5-tap binomial
+ * [1 4 6 4 1]/16 with reflect-101 borders; H pass over every row, then W pass, each accumulated tap by tap (j = 0..4 from 0.0f,
+ * fp32 products and sums): the host pyr_down on float32 input bit for bit.  H, W >= 3. */
+int bg_pyr_down_f32(const float* x, float* y, int planes, int H, int W, void* stream);
+/* sliced_wasserstein.py:76-81 (pyr_up) and the subtraction of :83-88 (one Laplacian level in one launch):
+ * out[planes, 2h, 2w] = pyr_up(low), or minuend - pyr_up(low) when minuend != NULL (out == minuend allowed).  pyr_up = zero-stuff
+ * to 2h x 2w, the same filter with reflect-101 on the stuffed grid, gain 4 after the filter; the taps on stuffed zeros add an exact
+ * zero and are skipped, so the result is the host pyr_up bit for bit.  h, w >= 2. */
+int bg_pyr_up_f32(const float* low, const float* minuend /* may be NULL */, float* out, int planes, int h, int w, void* stream);
+/* sliced_wasserstein.py:13-23 (get_descriptors_for_minibatch) from the centres the host drew: level[B,3,H,W]; cx_d, cy_d int32
+ * device vectors of B * per_image entries; desc[t, c, a, b] = level[t / per_image, c, cy[t] + b - half, cx[t] + a - half] with
+ * half = nhood / 2 -- the reference's transposed patch: a walks x, b walks y.  nhood odd, <= min(H, W).  The library cannot see
+ * device memory: EVERY centre MUST lie in [half, size - half) -- the caller checks the draws' range on the host. */
+int bg_swd_gather_f32(const float* level, const int32_t* cx_d, const int32_t* cy_d, float* desc, int B, int H, int W, int nhood,
+                      int per_image, void* stream);
+/* sliced_wasserstein.py:27-34 (finalize_descriptors) over desc[rows, 3, nhood, nhood], in place: per-channel mean and POPULATION
+ * standard deviation accumulated in float64 (two-stage partials in a fixed order, no atomics; the deviation is summed around the
+ * mean in a second pass), both rounded to fp32, then desc = (desc - mean32) / std32 as two fp32 operations.  A constant channel
+ * gives the IEEE result of the division.  stats_out (may be NULL): 3 x {mean, std} doubles on the device. */
+size_t bg_swd_standardize_workspace_bytes(int rows, int nhood);
+int bg_swd_standardize_f32(float* desc, int rows, int nhood, double* stats_out /* may be NULL */, void* ws, size_t ws_bytes, void* stream);
+/* np.sort(x, axis=1) in place over x[rows, n] (sliced_wasserstein.py:47-48, transposed): a data-oblivious bitonic network -- 4096-float chunks
+ * and the merge tails in LDS, one launch per compare-exchange distance above the chunk, indices >= n standing for +inf without a
+ * padded copy.  Finite input: the values of np.sort (-0.0 and +0.0 compare equal).  NaNs end up anywhere but never fault: the
+ * access pattern depends on (rows, n) only.  1 <= n <= 2^24, rows * n < 2^31. */
+int bg_sort_rows_f32(float* x, int rows, int n, void* stream);
+/* out[s] (double, device) = mean over e < seg of |a[s * seg + e] - b[s * seg + e]| (sliced_wasserstein.py:49-50): the difference in
+ * fp32, the sum in float64 in a fixed order.  One segment per direction repeat.  nseg <= 65535. */
+size_t bg_abs_diff_mean_workspace_bytes(size_t seg, int nseg);
+int bg_abs_diff_mean_f32(const float* a, const float* b, size_t seg, int nseg, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimiser: tf.keras.optimizers.Adam (wgan.py:56-61,141,167) ----------------------------- */
 /* lr_t = lr*sqrt(1-b2^t)/(1-b1^t) is computed by the caller (host) per step. */
 int bg_adam_f32(float* theta, float* m, float* v, const float* g, size_t n, float lr_t, float b1, float b2,
