@@ -40,13 +40,18 @@ def _data(B, H, W, Ci, Co, s, seed=0):
     return x, w, dy
 
 
+def _nan(shape):
+    """An output that starts as NaN: an element the kernel never writes cannot pass for a value a freed block left behind."""
+    return torch.full(tuple(shape), float("nan"), device="cuda")
+
+
 @pytest.mark.parametrize("B,H,W,Ci,Co,s", CASES)
 def test_conv_fwd(B, H, W, Ci, Co, s):
     from blurred_gan_amd import ops
     x, w, dy = _data(B, H, W, Ci, Co, s)
     ref = O.conv2d_fwd(x, w, s)
     wT = dev(np.transpose(w, (0, 1, 3, 2)))
-    y = ops.conv2d_fwd(dev(x), wT, torch.empty(ref.shape, device="cuda"), 5, s)
+    y = ops.conv2d_fwd(dev(x), wT, _nan(ref.shape), 5, s)
     torch.cuda.synchronize()
     np.testing.assert_allclose(y.cpu().numpy(), ref, rtol=1e-4, atol=conv_tol(25 * Ci, np.abs(ref).max()))
     # the transposed weight copy made by the library's own transpose kernel
@@ -59,7 +64,7 @@ def test_conv_bwd_data(B, H, W, Ci, Co, s):
     from blurred_gan_amd import ops
     x, w, dy = _data(B, H, W, Ci, Co, s, seed=1)
     ref = O.conv2d_bwd_data(dy, w, s, (H, W))
-    dx = ops.conv2d_bwd_data(dev(dy), dev(w), torch.empty(x.shape, device="cuda"), 5, s)
+    dx = ops.conv2d_bwd_data(dev(dy), dev(w), _nan(x.shape), 5, s)
     torch.cuda.synchronize()
     np.testing.assert_allclose(dx.cpu().numpy(), ref, rtol=1e-4, atol=conv_tol(25 * Co, np.abs(ref).max()))
 
@@ -385,10 +390,10 @@ def test_conv_random_shapes(B, H, W, Ci, Co, s):
     x, w, dy = _data(B, H, W, Ci, Co, s, seed=B * 1000 + H * 31 + W)
     wT = dev(np.transpose(w, (0, 1, 3, 2)))
     ref = O.conv2d_fwd(x, w, s)
-    y = ops.conv2d_fwd(dev(x), wT, torch.empty(ref.shape, device="cuda"), 5, s)
+    y = ops.conv2d_fwd(dev(x), wT, _nan(ref.shape), 5, s)
     np.testing.assert_allclose(y.cpu().numpy(), ref, rtol=1e-4, atol=conv_tol(25 * Ci, np.abs(ref).max()))
     refd = O.conv2d_bwd_data(dy, w, s, (H, W))
-    dx = ops.conv2d_bwd_data(dev(dy), dev(w), torch.empty(x.shape, device="cuda"), 5, s)
+    dx = ops.conv2d_bwd_data(dev(dy), dev(w), _nan(x.shape), 5, s)
     np.testing.assert_allclose(dx.cpu().numpy(), refd, rtol=1e-4, atol=conv_tol(25 * Co, np.abs(refd).max()))
     refw = O.conv2d_bwd_filter(x, dy, s, 5)
     nb = ops.conv2d_bwd_filter_workspace_bytes(B, H, W, Ci, Co, 5, s)
