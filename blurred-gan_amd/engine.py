@@ -3,9 +3,11 @@ gradient-penalty linearised forward on the HIP kernels.  There is no tape: every
 written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
 A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization] [+ LeakyReLU |
-tanh] [+ Dropout]; Reshape / Flatten are views.  Stage fusion on the device:
+tanh] [+ Dropout]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
+one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  Stage fusion on the device:
   conv (+bias) + LeakyReLU + Dropout      -> one launch (epilogue of the MFMA kernel)
   dgrad + LeakyReLU'/Dropout' of the stage below -> one launch (BG_EPI_MUL_GRAD epilogue)
+  pooling backward + LeakyReLU'/Dropout' of the stage below -> one launch (the upsample with ref / keep)
   BatchNormalization + LeakyReLU          -> stats pass + one apply pass
 """
 from __future__ import annotations
@@ -18,6 +20,9 @@ import torch
 
 from . import dist, ops
 from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_LRELU
+
+
+RESAMPLE = ("upsample", "avgpool")
 
 
 class Stage:
@@ -126,6 +131,10 @@ class _RowView:
         return lst[i]
 
 
+_GP_SHAPE_MESSAGE = ("gradient penalty second order supports the reference critic shape only: "
+                     "[Conv2D+LeakyReLU(+Dropout) | UpSampling2D | AveragePooling2D]* -> Flatten -> Dense(1) (demo_celeba.py:96-124)")
+
+
 class Net:
     def __init__(self, flat_layers, store):
         self.store = store
@@ -144,16 +153,19 @@ class Net:
             elif k in ("dense", "conv", "convT"):
                 cur = Stage(l, s)
                 self.stages.append(cur)
+            elif k in RESAMPLE:
+                cur = Stage(l, s)
+                self.stages.append(cur)
             elif k == "bn":
-                if cur is None or cur.bn is not None or cur.act is not None or cur.drop:
+                if cur is None or cur.kind in RESAMPLE or cur.bn is not None or cur.act is not None or cur.drop:
                     raise NotImplementedError("BatchNormalization must directly follow a linear layer")
                 cur.bn = l
             elif k == "lrelu":
-                if cur is None or cur.act is not None or cur.drop:
+                if cur is None or cur.kind in RESAMPLE or cur.act is not None or cur.drop:
                     raise NotImplementedError("LeakyReLU must follow a linear layer or its BatchNormalization")
                 cur.act, cur.alpha = "lrelu", l.alpha
             elif k == "dropout":
-                if cur is None or cur.drop or cur.bn is not None or cur.act != "lrelu":
+                if cur is None or cur.kind in RESAMPLE or cur.drop or cur.bn is not None or cur.act != "lrelu":
                     raise NotImplementedError("Dropout is supported after conv + LeakyReLU (demo_celeba.py:99-121)")
                 cur.drop = l.rate
             elif k in ("reshape", "flatten"):
@@ -165,6 +177,8 @@ class Net:
                 raise NotImplementedError("Dense + activation without BatchNormalization is not on the reference path")
             if st.act == "tanh" and st.bn is not None:
                 raise NotImplementedError("tanh after BatchNormalization is not on the reference path")
+        if self.stages and (self.stages[0].kind in RESAMPLE or self.stages[-1].kind in RESAMPLE):
+            raise NotImplementedError("UpSampling2D / AveragePooling2D must stand between two linear layers, not first or last in a network")
         self.out_shape = self.stages[-1].out_shape
         self.conv_layers = [st.lin for st in self.stages if st.kind in ("conv", "convT")]
         self._ctx = {}
@@ -325,6 +339,10 @@ class Net:
             xin = x.view(B, *st.in_shape)
             ctx.xin[i] = xin
             out = ctx.a[i]
+            if st.kind in RESAMPLE:
+                self._resample(st, xin, out)
+                x = out
+                continue
             tgt = ctx.z[i] if st.bn is not None else out
             bias = st.lin.vars.get("bias")
             keep = None
@@ -413,6 +431,14 @@ class Net:
                                      bn.vars["moving_variance"], eps=bn.epsilon, lrelu_alpha=st.alpha)
             x = out
         return x
+
+    @staticmethod
+    def _resample(st, x, y):
+        """Forward of a resampling stage; linear and parameter-free, so also its linearised forward in the gradient penalty."""
+        if st.kind == "upsample":
+            ops.upsample2x(x, y, 1.0)
+        else:
+            ops.pool2x_sum(x, y, 0.25)
 
     def predict(self, x, training=False):
         B = int(x.shape[0])
@@ -526,8 +552,8 @@ class Net:
             # latency-bound collective hides behind an MFMA kernel instead of sitting on the critical path of every layer.
             # (The filter gradient's split-K workspace and the statistics' partials share net.workspace(): the statistics
             # kernel has finished with it before the filter gradient is enqueued on the same stream.)
-            overlap = sync_bn and need_dw and prev is not None and prev.bn is not None
-            if need_dw and not overlap:
+            overlap = sync_bn and need_dw and prev is not None and prev.bn is not None and st.kind not in RESAMPLE
+            if need_dw and not overlap and st.kind not in RESAMPLE:
                 weight_grads()
             # ---- input gradient
             if i == 0 and not need_dx:
@@ -535,8 +561,28 @@ class Net:
                     for rng in deferred_ready:
                         reducer.ready(*rng)
                 return None
-            fuse = prev is not None and prev.fusable_grad and st.kind != "dense"
+            fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
             tgt = ctx.buf(ctx.dz, i - 1).view(B, *st.in_shape) if i > 0 else ctx.input_grad().view(B, *st.in_shape)
+            if st.kind == "upsample":         # transpose of the upsample; the stage below applies its own BN / activation backward
+                ops.pool2x_sum(dz.view(B, *st.out_shape), tgt, 1.0)
+                g, g_is_dz = tgt, False
+                continue
+            if st.kind == "avgpool":
+                dzp = dz.view(B, *st.out_shape)
+                if not fuse:
+                    ops.upsample2x(dzp, tgt, 0.25)
+                else:       # lands as the dz of the conv + LeakyReLU (+ Dropout) stage below: one launch instead of upsample + mul_grad
+                    pk = ctx.keep[i - 1] if (prev.drop and ctx.dropout_active) else None
+                    ref = ctx.a[i - 1]
+                    if pk is not None and ctx.drop_rows < B:        # masked rows first, the unmasked tail separately
+                        DR = ctx.drop_rows
+                        ops.upsample2x(dzp[:DR], tgt[:DR], 0.25, ref=ref[:DR], keep=pk, alpha=prev.alpha, grad_scale=1.0 / (1.0 - prev.drop))
+                        ops.upsample2x(dzp[DR:], tgt[DR:], 0.25, ref=ref[DR:], alpha=prev.alpha)
+                    else:
+                        ops.upsample2x(dzp, tgt, 0.25, ref=ref, keep=pk, alpha=prev.alpha,
+                                       grad_scale=1.0 / (1.0 - prev.drop) if pk is not None else 1.0)
+                g, g_is_dz = tgt, fuse
+                continue
             Bx = B
             dzx = dz
             if i == 0 and dx_rows is not None:        # the image gradient is wanted for samples [lo, hi) only
@@ -625,9 +671,11 @@ class Net:
                 ops.colsum(ctx.xin[i][lo:hi].reshape(Bh, K), st_.grad_of(lin, "kernel").view(K), Bh, K, ws, beta=1.0, scale=1.0)
                 if reducer is not None:
                     reducer.ready(*st_.train_range(lin, st.bn))
+            elif st.kind in RESAMPLE and not last:
+                # delta-bar_i = op(delta-bar_{i-1}): from the x-hat rows of a_{i-1} into those of a_i (dead after the backward)
+                self._resample(st, ctx.xin[i][lo:hi], ctx.a[i][lo:hi])
             else:
-                raise NotImplementedError("gradient penalty second order supports the reference critic shape only: "
-                                          "[Conv2D+LeakyReLU(+Dropout)]* -> Flatten -> Dense(1) (demo_celeba.py:96-124)")
+                raise NotImplementedError(_GP_SHAPE_MESSAGE)
 
     def gp_second_order(self, ctx: Context, v0, reducer=None):
         """SURVEY.md 8a, GP derivation step 2: one linearised forward of the critic on ``v0`` with the
@@ -658,6 +706,9 @@ class Net:
                 ops.colsum(v.view(B, K), st_.grad_of(lin, "kernel").view(K), B, K, ws, beta=1.0, scale=1.0)
                 if reducer is not None:
                     reducer.ready(*st_.train_range(lin, st.bn))
+            elif st.kind in RESAMPLE and not last:
+                vo = ctx.buf(ctx.v, i)
+                self._resample(st, v.view(B, *st.in_shape), vo)
+                v = vo
             else:
-                raise NotImplementedError("gradient penalty second order supports the reference critic shape only: "
-                                          "[Conv2D+LeakyReLU(+Dropout)]* -> Flatten -> Dense(1) (demo_celeba.py:96-124)")
+                raise NotImplementedError(_GP_SHAPE_MESSAGE)

@@ -162,6 +162,54 @@ class Dropout(Layer):
         self.rate = float(rate)
 
 
+def _channels_last(data_format):
+    return data_format is None or str(data_format).lower() == "channels_last"
+
+
+class UpSampling2D(Layer):
+    """tf.keras.layers.UpSampling2D: nearest-neighbour, factor 2 (the resize-convolution generator's resolution step)."""
+    kind = "upsample"
+
+    def __init__(self, size=(2, 2), data_format=None, interpolation="nearest", **kw):
+        super().__init__(**kw)
+        if _pair(size) != (2, 2):
+            raise NotImplementedError(f"UpSampling2D size {size!r}: only size 2 is supported")
+        if str(interpolation).lower() != "nearest":
+            raise NotImplementedError(f"UpSampling2D interpolation {interpolation!r}: only 'nearest' is supported")
+        if not _channels_last(data_format):
+            raise NotImplementedError("only data_format='channels_last' (NHWC) is supported")
+        self.size = (2, 2)
+
+    def out_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"UpSampling2D needs an [H, W, C] map, got {tuple(s)}")
+        return (2 * s[0], 2 * s[1], s[2])
+
+
+class AveragePooling2D(Layer):
+    """tf.keras.layers.AveragePooling2D: 2x2 pool, stride 2, on maps of even height and width."""
+    kind = "avgpool"
+
+    def __init__(self, pool_size=(2, 2), strides=None, padding="valid", data_format=None, **kw):
+        super().__init__(**kw)
+        if _pair(pool_size) != (2, 2):
+            raise NotImplementedError(f"AveragePooling2D pool_size {pool_size!r}: only a 2x2 pool is supported")
+        if strides is not None and _pair(strides) != (2, 2):
+            raise NotImplementedError(f"AveragePooling2D strides {strides!r}: only strides equal to the 2x2 pool are supported")
+        if str(padding).lower() not in ("valid", "same"):
+            raise NotImplementedError(f"AveragePooling2D padding {padding!r}")
+        if not _channels_last(data_format):
+            raise NotImplementedError("only data_format='channels_last' (NHWC) is supported")
+        self.pool_size = self.strides = (2, 2)
+
+    def out_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"AveragePooling2D needs an [H, W, C] map, got {tuple(s)}")
+        if s[0] % 2 or s[1] % 2:
+            raise NotImplementedError(f"AveragePooling2D on a map of odd height or width {tuple(s)} (Keras would drop the last row)")
+        return (s[0] // 2, s[1] // 2, s[2])
+
+
 class Reshape(Layer):
     kind = "reshape"
 

@@ -4,7 +4,12 @@
 (build-side definition for BASELINE.json's 64x64 configs: the 128 stack minus its outermost stage on each
 side, SURVEY.md 8a "Architecture note"), plus small test geometries ("tiny": MFMA-tileable channel
 counts on 8x8x3 images; "tiny_mnist": odd channel counts, 12x12x1, ConvT with fused tanh; "tiny_k3": the "tiny"
-stacks with 3x3 kernels -- every other architecture uses the demos' 5x5)."""
+stacks with 3x3 kernels -- every other architecture uses the demos' 5x5).
+
+Both stacks have a resampling variant with the same map sizes, variable counts and Dense input: ``upsampling="resize"`` replaces
+every stride-2 transposed convolution by nearest-neighbour UpSampling2D + a stride-1 Conv2D (the resize-convolution generator),
+``downsampling="pool"`` every stride-2 convolution by a stride-1 one whose LeakyReLU / Dropout output is average-pooled.  Such a
+stage convolves at the higher resolution: 4x the multiply-adds of the strided layer it replaces."""
 from __future__ import annotations
 
 from . import layers
@@ -26,8 +31,11 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 
 class DCGANGenerator(layers.Sequential):
-    def __init__(self, latent_size=None, arch="celeba128", *args, **kwargs):
+    def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", **kwargs):
         super().__init__(*args, **kwargs)
+        if upsampling not in ("transpose", "resize"):
+            raise ValueError(f"upsampling must be 'transpose' or 'resize', got {upsampling!r}")
+        self.upsampling = upsampling
         base, ch, convt, last = _G[arch]
         k = KSIZE.get(arch, 5)
         self.latent_size = latent_size or LATENT[arch]
@@ -38,7 +46,11 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, base, base, ch)
         hw = base
         for filters, stride, act in convt:
-            self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=False, activation=act))
+            if stride == 2 and upsampling == "resize":
+                self.add(layers.UpSampling2D())
+                self.add(layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=False, activation=act))
+            else:
+                self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=False, activation=act))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
             if act is None:
@@ -50,12 +62,18 @@ class DCGANGenerator(layers.Sequential):
 
 
 class DCGANDiscriminator(layers.Sequential):
-    def __init__(self, arch="celeba128", *args, **kwargs):
+    def __init__(self, arch="celeba128", *args, downsampling="stride", **kwargs):
         super().__init__(*args, **kwargs)
+        if downsampling not in ("stride", "pool"):
+            raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
+        self.downsampling = downsampling
+        pool = downsampling == "pool"
         for i, c in enumerate(_D[arch]):
             kw = dict(input_shape=list(IMAGE_SHAPE[arch])) if i == 0 else {}
-            self.add(layers.Conv2D(c, KSIZE.get(arch, 5), strides=2, padding="same", **kw))
+            self.add(layers.Conv2D(c, KSIZE.get(arch, 5), strides=1 if pool else 2, padding="same", **kw))
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
+            if pool:
+                self.add(layers.AveragePooling2D())
         self.add(layers.Flatten())
         self.add(layers.Dense(1, activation="linear"))

@@ -403,6 +403,28 @@ def copy_(dst, src):
     return dst
 
 
+def upsample2x(x, y, scale=1.0, ref=None, keep=None, alpha=LRELU_ALPHA, grad_scale=1.0):
+    """y[B,2H,2W,C] = scale * nearest-neighbour 2x upsample of x[B,H,W,C]; with ``ref`` (and ``keep``) what is written is further
+    multiplied by ``mul_grad``'s factor, as ``mul_grad(y, ref, y, keep, alpha, grad_scale)`` after the plain call would."""
+    _f32(x, y, ref)
+    B, H, W, Cc = x.shape
+    assert tuple(y.shape) == (B, 2 * H, 2 * W, Cc), (tuple(x.shape), tuple(y.shape))
+    assert ref is None or ref.numel() == y.numel()
+    assert keep is None or (ref is not None and keep.dtype == torch.uint8 and keep.numel() == y.numel())
+    check(_lib.load().bg_upsample2x_nhwc_f32(_ptr(x), _ptr(y), B, H, W, Cc, scale, _ptr(ref), _ptr(keep), alpha, grad_scale, _stream()),
+          "bg_upsample2x_nhwc_f32")
+    return y
+
+
+def pool2x_sum(x, y, scale=1.0):
+    """y[B,H,W,C] = scale * ((x00 + x01) + (x10 + x11)) over the 2x2 blocks of x[B,2H,2W,C]."""
+    _f32(x, y)
+    B, H, W, Cc = y.shape
+    assert tuple(x.shape) == (B, 2 * H, 2 * W, Cc), (tuple(x.shape), tuple(y.shape))
+    check(_lib.load().bg_pool2x_sum_nhwc_f32(_ptr(x), _ptr(y), B, H, W, Cc, scale, _stream()), "bg_pool2x_sum_nhwc_f32")
+    return y
+
+
 def wgangp_d_loss(fs, rs, norm_b, inv_gbs, gp_coef, e_drift, vec_scale, dfs, drs, metrics):
     B = fs.numel()
     check(_lib.load().bg_wgangp_d_loss(_ptr(fs), _ptr(rs), _ptr(norm_b), B, inv_gbs, gp_coef, e_drift, vec_scale, _ptr(dfs),

@@ -29,9 +29,10 @@ def make_dataset(batch_size, n_batches=None, seed=0):
 class DCGANGenerator(layers.Sequential):
     """demo_celeba.py:51-93."""
 
-    def __init__(self, latent_size=100, *args, **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", **kwargs):
         super().__init__(*args, **kwargs)
         self.latent_size = latent_size
+        resize = {"transpose": False, "resize": True}[upsampling]
         self.add(layers.Dense(4 * 4 * 512, use_bias=False, input_shape=(self.latent_size,)))
         self.add(layers.BatchNormalization())
         self.add(layers.LeakyReLU())
@@ -39,7 +40,11 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, 4, 4, 512)
         hw = 4
         for filters, stride in ((512, 1), (256, 2), (128, 2), (64, 2), (32, 2), (16, 2)):
-            self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding='same', use_bias=False))
+            if resize and stride == 2:      # resize-convolution: nearest-neighbour upsampling, then a stride-1 convolution
+                self.add(layers.UpSampling2D())
+                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=False))
+            else:
+                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding='same', use_bias=False))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
             self.add(layers.BatchNormalization())
@@ -51,13 +56,16 @@ class DCGANGenerator(layers.Sequential):
 class DCGANDiscriminator(layers.Sequential):
     """demo_celeba.py:96-124."""
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, downsampling="stride", **kwargs):
         super().__init__(*args, **kwargs)
+        pool = {"stride": False, "pool": True}[downsampling]
         for i, c in enumerate((16, 32, 64, 128, 256, 512)):
             kw = dict(input_shape=[128, 128, 3]) if i == 0 else {}
-            self.add(layers.Conv2D(c, 5, strides=2, padding='same', **kw))
+            self.add(layers.Conv2D(c, 5, strides=1 if pool else 2, padding='same', **kw))
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
+            if pool:
+                self.add(layers.AveragePooling2D())
         self.add(layers.Flatten())
         self.add(layers.Dense(1, activation="linear"))
 
@@ -72,6 +80,12 @@ def make_parser():
     parser.add_argument("--results_dir", default="results")
     parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
                         help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
+    parser.add_argument("--upsampling", default="transpose", choices=["transpose", "resize"],
+                        help="generator resolution steps: stride-2 Conv2DTranspose (default, the reference's) or nearest-neighbour "
+                             "UpSampling2D + stride-1 Conv2D (4x the multiply-adds of the layers it replaces)")
+    parser.add_argument("--downsampling", default="stride", choices=["stride", "pool"],
+                        help="critic resolution steps: stride-2 Conv2D (default, the reference's) or stride-1 Conv2D + AveragePooling2D "
+                             "(4x the multiply-adds of the layers it replaces)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -111,7 +125,7 @@ def main(argv=None):
         total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
-    gen, disc = DCGANGenerator(), DCGANDiscriminator()
+    gen, disc = DCGANGenerator(upsampling=args.upsampling), DCGANDiscriminator(downsampling=args.downsampling)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

@@ -31,9 +31,17 @@ def make_dataset(batch_size, n_batches=None, shuffle_buffer_size=256, seed=0):
 class DCGANGenerator(layers.Sequential):
     """demo_mnist.py:48-71."""
 
-    def __init__(self, latent_size=100, *args, **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", **kwargs):
         super().__init__(*args, **kwargs)
         self.latent_size = latent_size
+        resize = {"transpose": False, "resize": True}[upsampling]
+
+        def up2(filters, **kw):       # a resolution step: the reference's stride-2 Conv2DTranspose, or upsampling + stride-1 Conv2D
+            if resize:
+                self.add(layers.UpSampling2D())
+                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=False, **kw))
+            else:
+                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(2, 2), padding='same', use_bias=False, **kw))
         self.add(layers.Dense(7 * 7 * 256, use_bias=False, input_shape=(self.latent_size,)))
         self.add(layers.BatchNormalization())
         self.add(layers.LeakyReLU())
@@ -43,25 +51,31 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, 7, 7, 128)
         self.add(layers.BatchNormalization())
         self.add(layers.LeakyReLU())
-        self.add(layers.Conv2DTranspose(64, (5, 5), strides=(2, 2), padding='same', use_bias=False))
+        up2(64)
         assert self.output_shape == (None, 14, 14, 64)
         self.add(layers.BatchNormalization())
         self.add(layers.LeakyReLU())
-        self.add(layers.Conv2DTranspose(1, (5, 5), strides=(2, 2), padding='same', use_bias=False, activation='tanh'))
+        up2(1, activation='tanh')
         assert self.output_shape == (None, 28, 28, 1)
 
 
 class DCGANDiscriminator(layers.Sequential):
     """demo_mnist.py:74-86."""
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, downsampling="stride", **kwargs):
         super().__init__(*args, **kwargs)
-        self.add(layers.Conv2D(64, (5, 5), strides=(2, 2), padding='same', input_shape=[28, 28, 1]))
+        pool = {"stride": False, "pool": True}[downsampling]
+        strides = (1, 1) if pool else (2, 2)
+        self.add(layers.Conv2D(64, (5, 5), strides=strides, padding='same', input_shape=[28, 28, 1]))
         self.add(layers.LeakyReLU())
         self.add(layers.Dropout(0.3))
-        self.add(layers.Conv2D(128, (5, 5), strides=(2, 2), padding='same'))
+        if pool:
+            self.add(layers.AveragePooling2D())
+        self.add(layers.Conv2D(128, (5, 5), strides=strides, padding='same'))
         self.add(layers.LeakyReLU())
         self.add(layers.Dropout(0.3))
+        if pool:
+            self.add(layers.AveragePooling2D())
         self.add(layers.Flatten())
         self.add(layers.Dense(1))
 
@@ -76,6 +90,12 @@ def make_parser():
     parser.add_argument("--results_dir", default="results")
     parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
                         help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
+    parser.add_argument("--upsampling", default="transpose", choices=["transpose", "resize"],
+                        help="generator resolution steps: stride-2 Conv2DTranspose (default, the reference's) or nearest-neighbour "
+                             "UpSampling2D + stride-1 Conv2D (4x the multiply-adds of the layers it replaces)")
+    parser.add_argument("--downsampling", default="stride", choices=["stride", "pool"],
+                        help="critic resolution steps: stride-2 Conv2D (default, the reference's) or stride-1 Conv2D + AveragePooling2D "
+                             "(4x the multiply-adds of the layers it replaces)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -122,8 +142,8 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "mnist") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
-    gen = DCGANGenerator()
-    disc = DCGANDiscriminator()
+    gen = DCGANGenerator(upsampling=args.upsampling)
+    disc = DCGANDiscriminator(downsampling=args.downsampling)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

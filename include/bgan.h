@@ -271,6 +271,24 @@ int bg_scale_f32(float* x, float v, size_t n, void* stream);
    program records like any other, which a runtime memcpy would not be) */
 int bg_copy_f32(float* dst, const float* src, size_t n, void* stream);
 
+/* ---- resampling: tf.keras.layers.UpSampling2D(2, "nearest") / AveragePooling2D(2) over NHWC fp32 maps --------------------
+ * Two linear, parameter-free operators, each the transpose of the other: UpSampling2D forward = upsample at scale 1, backward =
+ * pool-sum at scale 1; AveragePooling2D forward = pool-sum at scale 0.25, backward = upsample at scale 0.25; the gradient
+ * penalty's linearised forward of either layer is its forward.  H, W are the LOW-resolution map's in both calls.  C % 4 == 0
+ * moves float4s and wants every pointer 16-byte aligned (BG_ERR_BAD_ALIGNMENT otherwise); any other C goes one float at a time
+ * with no alignment demand.  Null x / y: BG_ERR_NULL; a non-positive dimension: BG_ERR_BAD_SHAPE.  A refused call launches
+ * nothing.  Indices are formed in 64 bits.  Neither call takes a step-program binding. */
+/* y[b, 2i+di, 2j+dj, c] = scale * x[b, i, j, c], di, dj in {0, 1}: x[B,H,W,C] -> y[B,2H,2W,C].  With ref (shape of y; keep, uint8 of
+ * the same shape, may come with it) every written element is further multiplied by bg_mul_grad_f32's factor
+ * (ref > 0 ? 1 : alpha) [* keep ? grad_scale : 0]: the result equals this call without ref followed by bg_mul_grad_f32 on its
+ * output, bit for bit -- a pooling layer's backward written straight as the dz of the conv + LeakyReLU (+ Dropout) stage below
+ * it.  ref and keep must not overlap y. */
+int bg_upsample2x_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, float scale, const float* ref /* may be NULL */,
+                           const uint8_t* keep /* may be NULL */, float alpha, float grad_scale, void* stream);
+/* y[b, i, j, c] = scale * ((x[b,2i,2j,c] + x[b,2i,2j+1,c]) + (x[b,2i+1,2j,c] + x[b,2i+1,2j+1,c])): x[B,2H,2W,C] -> y[B,H,W,C], summed
+ * in exactly this order. */
+int bg_pool2x_sum_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, float scale, void* stream);
+
 /* ---- losses (wgan.py:128-130,155-157,272-285) ----------------------------------------------- */
 /* From scores fs[B], rs[B] and the per-sample norms n[B] of the GP gradient:
  *   metrics_d[0..5] = mean(fs), mean(rs), disc_loss (mean of the [B] vector), gp_term, mean(norm_term), GP
