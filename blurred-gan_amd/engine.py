@@ -9,6 +9,9 @@ one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the o
   dgrad + LeakyReLU'/Dropout' of the stage below -> one launch (BG_EPI_MUL_GRAD epilogue)
   pooling backward + LeakyReLU'/Dropout' of the stage below -> one launch (the upsample with ref / keep)
   BatchNormalization + LeakyReLU          -> stats pass + one apply pass
+
+Net.forward and Net.backward are input / pass set-up, a loop over the stages, and one helper per concern (DESIGN.md §5
+"Engine map"); tests/test_engine_trace_cpu.py holds the order and the arguments of everything they enqueue.
 """
 from __future__ import annotations
 
@@ -35,13 +38,40 @@ class Stage:
         self.act = getattr(lin, "activation", None)
         self.alpha = 1.0
         self.drop = None
+        self.mask_index = None      # which of the pass's Dropout masks is this stage's (forward(masks=...))
+        # inference BatchNorm behind a bias-free conv (the generator inside the D-step) is folded into the conv's epilogue: no z,
+        # no BatchNorm pass (set once the stage is complete)
+        self.folds_inference_bn = False
+        # conv stages: (H, W, Cin, Cout, k, stride) on the conv-INPUT side.  A Conv2DTranspose is the data gradient of the conv
+        # whose input side is this layer's output, with the same kernel array
+        self.geom = None
+        if self.kind == "conv":
+            self.geom = (*self.in_shape, lin.filters, lin.k, lin.stride)
+        elif self.kind == "convT":
+            self.geom = (*self.out_shape[:2], lin.filters, self.in_shape[2], lin.k, lin.stride)
 
     @property
     def fusable_grad(self):
         return self.bn is None and self.act == "lrelu"
 
+    @property
+    def drop_scale(self):
+        return 1.0 / (1.0 - self.drop) if self.drop else 1.0
 
-class Context:
+    def bn_args(self):
+        """The BatchNorm's parameters as the keywords every ops.bn_* function names them by (in bn_fold's positional order)."""
+        v = self.bn.vars
+        return dict(gamma=v["gamma"], beta=v["beta"], moving_mean=v["moving_mean"], moving_var=v["moving_variance"], eps=self.bn.epsilon)
+
+
+class _StageBuffers:
+    def buf(self, lst, i):
+        if lst[i] is None:
+            lst[i] = torch.empty((self.B,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
+        return lst[i]
+
+
+class Context(_StageBuffers):
     """Activation / gradient buffers of one pass at a fixed batch size (caller-owned HBM)."""
 
     def __init__(self, net, B, device, drop_rows=None):
@@ -79,20 +109,35 @@ class Context:
         self.keep_rate = rates.pop() if len(rates) == 1 else None      # None: stages differ, draw per stage
         self._net, self._device = net, device
         self._extra = {}
+        self._bn_grad_scratch = {}
         self.dropout_active = False
 
     def keep_elems(self, i):
         """Output elements of stage i covered by its dropout mask (0 = all of them): the bg_epilogue.keep_elems field."""
         return 0 if self.drop_rows >= self.B else self.drop_rows * int(np.prod(self._net.stages[i].out_shape))
 
+    def dropout(self, i):
+        """(keep mask or None, 1 / (1 - rate), keep_elems) of stage i as this pass's last forward left it: what the LeakyReLU
+        epilogue and the three LeakyReLU' / Dropout' sites of the backward multiply by.  (None, 1.0, 0) without Dropout or
+        with training=False."""
+        st = self._net.stages[i]
+        if not (st.drop and self.dropout_active):
+            return None, 1.0, 0
+        return self.keep[i], st.drop_scale, self.keep_elems(i)
+
+    def masked_then_tail(self, i, launch):
+        """Runs ``launch(rows, keep, scale)`` for the Dropout' factor of stage i over the whole batch -- as one call, or, where
+        the masks cover the first drop_rows samples only, for the masked rows first and for the unmasked tail separately."""
+        keep, scale, _ = self.dropout(i)
+        if keep is not None and self.drop_rows < self.B:
+            launch(slice(0, self.drop_rows), keep, scale)
+            launch(slice(self.drop_rows, None), None, 1.0)
+        else:
+            launch(slice(None), keep, scale)
+
     def rows(self, lo, hi):
         """A view of this pass restricted to samples [lo, hi): what gp_second_order needs of the x-hat rows of a merged pass."""
         return _RowView(self, lo, hi)
-
-    def buf(self, lst, i):
-        if lst[i] is None:
-            lst[i] = torch.empty((self.B,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
-        return lst[i]
 
     def bn_partials(self, i, rows, C):
         """Room for the per-workgroup BatchNorm statistics the conv of stage i leaves behind (bg_epilogue.stats)."""
@@ -108,13 +153,19 @@ class Context:
             self._extra[key] = torch.empty(2 * C, dtype=torch.float32, device=self._device)
         return self._extra[key]
 
+    def bn_grad_scratch(self, i, C):
+        """(dgamma, dbeta) of stage i's BatchNorm for a backward that wants no weight gradients (the kernels write them anyway)."""
+        if i not in self._bn_grad_scratch:
+            self._bn_grad_scratch[i] = tuple(torch.empty(C, dtype=torch.float32, device=self._device) for _ in range(2))
+        return self._bn_grad_scratch[i]
+
     def input_grad(self):
         if self.din is None:
             self.din = torch.empty((self.B,) + self._net.in_shape, dtype=torch.float32, device=self._device)
         return self.din
 
 
-class _RowView:
+class _RowView(_StageBuffers):
     """Samples [lo, hi) of a Context: sliced activations / gradients, own scratch for the linearised forward."""
 
     def __init__(self, ctx, lo, hi):
@@ -125,10 +176,22 @@ class _RowView:
         self.v = ctx._extra.setdefault(key, [None] * len(ctx.a))
         self._net, self._device = ctx._net, ctx._device
 
-    def buf(self, lst, i):
-        if lst[i] is None:
-            lst[i] = torch.empty((self.B,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
-        return lst[i]
+
+class _BackwardPass:
+    """What one Net.backward call carries from stage to stage."""
+
+    def __init__(self, ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, sync_bn):
+        self.ctx, self.need_dw, self.beta, self.scale, self.reducer = ctx, need_dw, beta, scale, reducer
+        self.dw_rows = ctx.B if dw_rows is None else int(dw_rows)
+        self.defer_conv_dw, self.sync_bn = defer_conv_dw, sync_bn
+        self.pending_stats = None       # SyncBN: the all-reduce of the NEXT (lower) stage's backward statistics, in flight
+        self.deferred_ready = []        # SyncBN overlap: gradient slices finished but not yet handed to the reducer
+
+    def release_deferred(self):
+        if self.reducer is not None:
+            for rng in self.deferred_ready:
+                self.reducer.ready(*rng)
+        self.deferred_ready.clear()
 
 
 _GP_SHAPE_MESSAGE = ("gradient penalty second order supports the reference critic shape only: "
@@ -144,16 +207,14 @@ class Net:
         self.stages: List[Stage] = []
         self.in_shape = tuple(flat_layers[0][1])
         cur = None
+        n_masks = 0
         for idx, (l, s) in enumerate(flat_layers):
             k = l.kind
             if k == "blur":
                 if idx != 0:
                     raise NotImplementedError("GaussianBlur2D is only supported as the first layer (blurred_gan.py:31-34)")
                 self.blur = l
-            elif k in ("dense", "conv", "convT"):
-                cur = Stage(l, s)
-                self.stages.append(cur)
-            elif k in RESAMPLE:
+            elif k in ("dense", "conv", "convT") + RESAMPLE:
                 cur = Stage(l, s)
                 self.stages.append(cur)
             elif k == "bn":
@@ -168,11 +229,14 @@ class Net:
                 if cur is None or cur.kind in RESAMPLE or cur.drop or cur.bn is not None or cur.act != "lrelu":
                     raise NotImplementedError("Dropout is supported after conv + LeakyReLU (demo_celeba.py:99-121)")
                 cur.drop = l.rate
+                if cur.drop:
+                    cur.mask_index, n_masks = n_masks, n_masks + 1
             elif k in ("reshape", "flatten"):
                 pass
             else:
                 raise NotImplementedError(f"layer kind {k!r}")
         for st in self.stages:
+            st.folds_inference_bn = st.bn is not None and st.kind != "dense" and st.lin.vars.get("bias") is None
             if st.kind == "dense" and st.bn is None and st.act is not None:
                 raise NotImplementedError("Dense + activation without BatchNormalization is not on the reference path")
             if st.act == "tanh" and st.bn is not None:
@@ -184,6 +248,7 @@ class Net:
         self._ctx = {}
         self._ws = None
         self._taps_cache = {}
+        self._taps_ring = {"i": 0, "bufs": [], "evs": []}     # pinned staging of the tap uploads (blur_taps)
         self._splitk_bytes = {}
         self.rng_offset = 0
         self.conv_math = "fp32"   # conv forward / data-gradient math of every call site below (ops.CONV_MATH; WGAN(conv_math=...))
@@ -214,6 +279,27 @@ class Net:
             nb = self._splitk_bytes[key] = ops.conv2d_splitk_workspace_bytes(bwd_data, B, H, W, Cin, Cout, k, stride)
         return ops.epilogue(mode, ws=self.workspace(nb) if nb else None, **kw)
 
+    def _conv(self, st, x, y, transpose, mode, **kw):
+        """One launch of conv stage ``st`` with an epilogue, in one of its two directions.  Apply (the layer's forward): Conv2D ->
+        conv2d_fwd with the transposed kernel copy, Conv2DTranspose -> conv2d_bwd_data with the kernel array.  ``transpose``
+        (its input gradient): the other way round.  Returns the epilogue (conv2d_stats_rows reads it)."""
+        bwd_data = (st.kind == "convT") != transpose
+        lin = st.lin
+        epi = self._epi(bwd_data, x.size(0), *st.geom, mode, **kw)
+        if bwd_data:
+            ops.conv2d_bwd_data(x, lin.vars["kernel"], y, lin.k, lin.stride, epi, math=self.conv_math)
+        else:
+            ops.conv2d_fwd(x, self.store.transposed_kernel(lin), y, lin.k, lin.stride, epi, math=self.conv_math)
+        return epi
+
+    def _filter_grad(self, st, a, dz, beta, scale):
+        """store.grad[kernel] = beta * old + scale * wgrad of conv stage ``st`` from its input ``a`` and output gradient ``dz``
+        (for a Conv2DTranspose the two swap sides)."""
+        x, dy = (a, dz) if st.kind == "conv" else (dz, a)
+        dW = self.store.grad_of(st.lin, "kernel")
+        nb = ops.conv2d_bwd_filter_workspace_bytes(x.size(0), *st.geom)
+        ops.conv2d_bwd_filter(x, dy, dW, st.lin.k, st.lin.stride, beta, scale, self.workspace(nb) if nb else None)
+
     def prepare_weights(self):
         """(Re)builds the transposed kernel copies the 'other direction' of each conv needs."""
         self.store.refresh_transposed(self.conv_layers)
@@ -234,7 +320,7 @@ class Net:
             assert len(taps) == nt
             if nt > 1024:
                 raise NotImplementedError(f"blur with {nt} taps (> 1024)")
-            ring = self.__dict__.setdefault("_taps_ring", {"i": 0, "bufs": [], "evs": []})
+            ring = self._taps_ring
             if not ring["bufs"]:
                 for _ in range(8):
                     ring["bufs"].append(torch.empty(1024, dtype=torch.float32, pin_memory=self.device.type == "cuda"))
@@ -278,159 +364,129 @@ class Net:
         fly (bg_blur3_lerp_nhwc_f32); otherwise x-hat is written to ``lerp_out`` by bg_lerp_f32 and joins the list."""
         if self.store.tr_dirty:
             self.prepare_weights()
+        x = self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)
+        ctx.dropout_active = bool(training)
+        # one launch draws the masks of all stages; where their rates differ, or masks are handed in, each stage sets its own
+        one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
+        if one_draw:
+            ops.keep_mask(ctx.keep_flat[:ctx.keep_total], 1.0 - ctx.keep_rate, seed, counter=(self, "rng_offset"))
+        folded = () if training else self._fold_inference_bns(ctx)
+        for i, st in enumerate(self.stages):
+            xin = ctx.xin[i] = x.view(ctx.B, *st.in_shape)
+            x = ctx.a[i]
+            if st.kind in RESAMPLE:
+                self._resample(st, xin, x)
+            else:
+                if st.drop and training and masks is not None:
+                    ctx.keep[i].copy_(masks[st.mask_index].view(ctx.keep[i].shape))
+                elif st.drop and training and not one_draw:
+                    ops.keep_mask(ctx.keep[i], 1.0 - st.drop, seed, counter=(self, "rng_offset"))
+                self._linear_forward(ctx, i, st, xin, x, training, i in folded)
+        return x
+
+    def _assemble_input(self, ctx, inputs, lerp_alpha, lerp_out):
+        """The pass's input batch: the single tensor itself, or ctx.a0 filled from the list -- through the blur where the network
+        starts with one (per slice, or all three slices of a ``lerp_alpha`` pass in one launch), by copies otherwise."""
         if not isinstance(inputs, (list, tuple)):
             inputs = [inputs]
-        B = ctx.B
-        fused3 = False
         if lerp_alpha is not None:
             f, r = inputs
             n = int(f.shape[0])
-            assert 3 * n == B
+            assert 3 * n == ctx.B
             if self.blur is not None:
                 H, W, C = self.in_shape
                 taps, nt = self.blur_taps(H, W)
-                fused3 = not os.environ.get("BGAN_NO_FUSED_BLUR3") and ops.blur3_lerp_supported(n, H, W, C, nt)
-            if fused3:
-                with ops.trace_range("blur"):
-                    ops.blur3_lerp(f.view(n, *self.in_shape), r.view(n, *self.in_shape), lerp_alpha, ctx.a0, taps, nt)
-            else:
-                inputs = [f, r, ops.lerp(r, f, lerp_alpha, lerp_out)]
-        assert fused3 or sum(int(t.shape[0]) for t in inputs) == B, "batch mismatch"
-        if fused3:
-            x = ctx.a0
-        elif self.blur is not None:
-            o = 0
-            for t in inputs:
-                n = int(t.shape[0])
+                if not os.environ.get("BGAN_NO_FUSED_BLUR3") and ops.blur3_lerp_supported(n, H, W, C, nt):
+                    with ops.trace_range("blur"):
+                        ops.blur3_lerp(f.view(n, *self.in_shape), r.view(n, *self.in_shape), lerp_alpha, ctx.a0, taps, nt)
+                    return ctx.a0
+            inputs = [f, r, ops.lerp(r, f, lerp_alpha, lerp_out)]
+        assert sum(int(t.shape[0]) for t in inputs) == ctx.B, "batch mismatch"
+        if self.blur is None and len(inputs) == 1:
+            return inputs[0]
+        o = 0
+        for t in inputs:
+            n = int(t.shape[0])
+            if self.blur is not None:
                 self.apply_blur(t.view(n, *self.in_shape), ctx.a0[o:o + n])
-                o += n
-            x = ctx.a0
-        elif len(inputs) == 1:
-            x = inputs[0]
-        else:
-            o = 0
-            for t in inputs:
-                n = int(t.shape[0])
-                ops.copy_(ctx.a0[o:o + n], t.view(n, *self.in_shape).contiguous())
-                o += n
-            x = ctx.a0
-        ctx.dropout_active = bool(training)
-        mi = 0
-        drawn = False
-        if training and masks is None and ctx.keep_rate is not None and ctx.keep_total:
-            ops.keep_mask(ctx.keep_flat[:ctx.keep_total], 1.0 - ctx.keep_rate, seed, counter=(self, "rng_offset"))
-            drawn = True
-        folded = ()
-        if not training:
-            # inference BatchNorms (the generator inside the D-step): every layer's fold in ONE launch ahead of the first conv
-            # instead of a tiny launch between each pair of convs (two kernel boundaries where one would do)
-            fl = [(j, s2) for j, s2 in enumerate(self.stages)
-                  if s2.bn is not None and s2.kind != "dense" and s2.lin.vars.get("bias") is None]
-            if 1 < len(fl) <= ops.FOLD_MAX:
-                args = []
-                for j, s2 in fl:
-                    Cj = s2.out_shape[-1]
-                    sc = ctx.bn_sums(j, Cj)
-                    v = s2.bn.vars
-                    args.append((v["gamma"], v["beta"], v["moving_mean"], v["moving_variance"], s2.bn.epsilon, sc[:Cj], sc[Cj:]))
-                ops.bn_fold_many(args)
-                folded = {j for j, _ in fl}
-        for i, st in enumerate(self.stages):
-            xin = x.view(B, *st.in_shape)
-            ctx.xin[i] = xin
-            out = ctx.a[i]
-            if st.kind in RESAMPLE:
-                self._resample(st, xin, out)
-                x = out
-                continue
-            tgt = ctx.z[i] if st.bn is not None else out
-            bias = st.lin.vars.get("bias")
-            keep = None
-            if st.drop:
-                if training:
-                    keep = ctx.keep[i]
-                    if masks is not None:
-                        keep.copy_(masks[mi].view(keep.shape))
-                    elif not drawn:
-                        ops.keep_mask(keep, 1.0 - st.drop, seed, counter=(self, "rng_offset"))
-                mi += 1
-            stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
-            if st.kind == "dense":
-                K, N = st.in_shape[0], st.out_shape[0]
-                ops.gemm(xin, st.lin.vars["kernel"], tgt, B, N, K, bias=bias)
             else:
-                lin = st.lin
-                if st.kind == "conv":
-                    geom = (False, B, st.in_shape[0], st.in_shape[1], st.in_shape[2], lin.filters, lin.k, lin.stride)
-                else:           # ConvT forward == data-gradient of the conv whose input side is this layer's output
-                    geom = (True, B, st.out_shape[0], st.out_shape[1], lin.filters, st.in_shape[2], lin.k, lin.stride)
-                fold_bn = st.bn is not None and not training and bias is None
-                if fold_bn:
-                    # inference BatchNorm (generator inside the D-step) folded into the conv epilogue: no z, no BN pass
-                    C = st.out_shape[-1]
-                    sc = ctx.bn_sums(i, C)
-                    bn = st.bn
-                    if i not in folded:
-                        ops.bn_fold(bn.vars["gamma"], bn.vars["beta"], bn.vars["moving_mean"], bn.vars["moving_variance"], bn.epsilon,
-                                    sc[:C], sc[C:])
-                    epi = self._epi(*geom, EPI_AFFINE_LRELU, bias=sc[C:], ref=sc[:C], alpha=st.alpha)
-                    tgt = out
-                elif st.bn is not None:
-                    # training BatchNorm behind a bias-free conv: the MFMA kernel leaves the column sums of what it stores
-                    # (one row per workgroup); at most one workgroup per 32 output rows and sub-pixel phase
-                    stats = None
-                    # under SyncBN the statistics ride in the conv's epilogue (the separate statistics pass would be two more
-                    # launches on the forward critical path beside every exchange); single-device: opt-in, see __init__
-                    if training and bias is None and (self.fuse_bn_stats or (self.sync_bn and dist.collectives_active()
-                                                                           and not os.environ.get("BGAN_NO_FUSED_BN_STATS"))):
-                        C = st.out_shape[-1]
-                        stats = ctx.bn_partials(i, int(np.prod((B,) + st.out_shape[:-1])) // 32 + 64, C)
-                    epi = self._epi(*geom, EPI_NONE, bias=bias, stats=stats)
-                elif st.act == "lrelu":
-                    epi = self._epi(*geom, EPI_BIAS_LRELU, bias=bias, keep=keep, alpha=st.alpha,
-                                    scale=1.0 / (1.0 - st.drop) if st.drop else 1.0,
-                                    keep_elems=ctx.keep_elems(i) if keep is not None else 0)
-                elif st.act == "tanh":
-                    epi = self._epi(*geom, EPI_TANH, bias=bias)
-                else:
-                    epi = self._epi(*geom, EPI_NONE, bias=bias)
-                if st.kind == "conv":
-                    ops.conv2d_fwd(xin, self.store.transposed_kernel(st.lin), tgt, st.lin.k, st.lin.stride, epi, math=self.conv_math)
-                else:   # Conv2DTranspose forward == data-gradient of the conv with the same kernel array
-                    ops.conv2d_bwd_data(xin, st.lin.vars["kernel"], tgt, st.lin.k, st.lin.stride, epi, math=self.conv_math)
-                stat_rows = ops.conv2d_stats_rows(epi) if st.bn is not None else 0
-            if st.bn is not None and not (st.kind != "dense" and not training and bias is None):
-                C = st.out_shape[-1]
-                M = tgt.numel() // C
-                bn = st.bn
-                if training and self.sync_bn and dist.collectives_active():
-                    # SyncBN (SURVEY.md 8e): batch statistics over the GLOBAL batch -- all-reduce the per-channel sums
-                    sums = ctx.bn_sums(i, C)
-                    if stat_rows:
-                        ops.bn_sums_from_partials(ctx.bn_partials(i, stat_rows, C), stat_rows, C, sums)
-                    else:
-                        ws = self.workspace(ops._lib.load().bg_bn_workspace_bytes(M, C))
-                        ops.bn_stats(tgt, M, C, sums, ws)
-                    dist.all_reduce_sum_(sums)
-                    # finalize + apply in one launch: with the statistics out of the conv's epilogue the chain around the
-                    # exchange is two launches per layer (partials -> sums, this)
-                    ops.bn_finalize_apply(sums, M * dist.world_size(), tgt, out, M, C, bn.vars["gamma"], bn.vars["beta"], ctx.mean[i],
-                                          ctx.inv[i], bn.vars["moving_mean"], bn.vars["moving_variance"], eps=bn.epsilon,
-                                          momentum=bn.momentum, unbiased=(len(st.out_shape) == 3), lrelu_alpha=st.alpha)
-                elif training and stat_rows:
-                    ops.bn_train_fwd_partials(ctx.bn_partials(i, stat_rows, C), stat_rows, tgt, out, M, C, bn.vars["gamma"], bn.vars["beta"],
-                                              bn.vars["moving_mean"], bn.vars["moving_variance"], ctx.mean[i], ctx.inv[i], eps=bn.epsilon,
-                                              momentum=bn.momentum, unbiased=(len(st.out_shape) == 3), lrelu_alpha=st.alpha)
-                elif training:
-                    ws = self.workspace(ops._lib.load().bg_bn_workspace_bytes(M, C))
-                    ops.bn_train_fwd(tgt, out, M, C, bn.vars["gamma"], bn.vars["beta"], bn.vars["moving_mean"],
-                                     bn.vars["moving_variance"], ctx.mean[i], ctx.inv[i], ws, eps=bn.epsilon,
-                                     momentum=bn.momentum, unbiased=(len(st.out_shape) == 3), lrelu_alpha=st.alpha)
-                else:
-                    ops.bn_infer_fwd(tgt, out, M, C, bn.vars["gamma"], bn.vars["beta"], bn.vars["moving_mean"],
-                                     bn.vars["moving_variance"], eps=bn.epsilon, lrelu_alpha=st.alpha)
-            x = out
-        return x
+                ops.copy_(ctx.a0[o:o + n], t.view(n, *self.in_shape).contiguous())
+            o += n
+        return ctx.a0
+
+    def _fold_inference_bns(self, ctx):
+        """Inference BatchNorms (the generator inside the D-step): every layer's fold in ONE launch ahead of the first conv instead
+        of a tiny launch between each pair of convs (two kernel boundaries where one would do).  Returns the stages it folded."""
+        fl = [j for j, st in enumerate(self.stages) if st.folds_inference_bn]
+        if not 1 < len(fl) <= ops.FOLD_MAX:
+            return ()
+        ops.bn_fold_many([(*self.stages[j].bn_args().values(), *self._fold_out(ctx, j)) for j in fl])
+        return set(fl)
+
+    def _fold_out(self, ctx, i):
+        """(scale, shift) of stage i's folded BatchNorm: the halves of its sums buffer, unused in inference."""
+        C = self.stages[i].out_shape[-1]
+        sc = ctx.bn_sums(i, C)
+        return sc[:C], sc[C:]
+
+    def _linear_forward(self, ctx, i, st, xin, out, training, folded):
+        """Stage i's linear op with what its epilogue fuses (bias, activation, Dropout, folded inference BatchNorm), then its
+        BatchNorm + LeakyReLU pass where it has one of its own."""
+        bias = st.lin.vars.get("bias")
+        tgt = ctx.z[i] if st.bn is not None else out
+        stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
+        if st.kind == "dense":
+            ops.gemm(xin, st.lin.vars["kernel"], tgt, ctx.B, st.out_shape[0], st.in_shape[0], bias=bias)
+        elif st.folds_inference_bn and not training:
+            scale, shift = self._fold_out(ctx, i)
+            if not folded:
+                ops.bn_fold(**st.bn_args(), scale_out=scale, shift_out=shift)
+            self._conv(st, xin, out, False, EPI_AFFINE_LRELU, bias=shift, ref=scale, alpha=st.alpha)
+            return
+        elif st.bn is not None:
+            # training BatchNorm behind a bias-free conv: the MFMA kernel leaves the column sums of what it stores
+            # (one row per workgroup); at most one workgroup per 32 output rows and sub-pixel phase
+            stats = None
+            # under SyncBN the statistics ride in the conv's epilogue (the separate statistics pass would be two more
+            # launches on the forward critical path beside every exchange); single-device: opt-in, see __init__
+            if training and bias is None and (self.fuse_bn_stats or (self.sync_bn and dist.collectives_active()
+                                                                   and not os.environ.get("BGAN_NO_FUSED_BN_STATS"))):
+                stats = ctx.bn_partials(i, int(np.prod((ctx.B,) + st.out_shape[:-1])) // 32 + 64, st.out_shape[-1])
+            stat_rows = ops.conv2d_stats_rows(self._conv(st, xin, tgt, False, EPI_NONE, bias=bias, stats=stats))
+        elif st.act == "lrelu":
+            keep, _, keep_elems = ctx.dropout(i)
+            # the scale is the stage's in inference too, as this launch has always been made (the kernel reads it with a mask only)
+            self._conv(st, xin, tgt, False, EPI_BIAS_LRELU, bias=bias, keep=keep, alpha=st.alpha, scale=st.drop_scale, keep_elems=keep_elems)
+        else:
+            self._conv(st, xin, tgt, False, EPI_TANH if st.act == "tanh" else EPI_NONE, bias=bias)
+        if st.bn is not None:
+            self._bn_forward(ctx, i, st, tgt, out, training, stat_rows)
+
+    def _bn_forward(self, ctx, i, st, tgt, out, training, stat_rows):
+        """out = LeakyReLU(BatchNorm(tgt)) of stage i, by the route the pass calls for: inference, SyncBN, statistics partials the
+        conv left behind (``stat_rows``), or the plain training pass."""
+        C = st.out_shape[-1]
+        M = tgt.numel() // C
+        if not training:
+            ops.bn_infer_fwd(tgt, out, M, C, **st.bn_args(), lrelu_alpha=st.alpha)
+            return
+        train = dict(st.bn_args(), save_mean=ctx.mean[i], save_inv=ctx.inv[i], momentum=st.bn.momentum,
+                     unbiased=(len(st.out_shape) == 3), lrelu_alpha=st.alpha)
+        if self.sync_bn and dist.collectives_active():
+            # SyncBN (SURVEY.md 8e): batch statistics over the GLOBAL batch -- all-reduce the per-channel sums
+            sums = ctx.bn_sums(i, C)
+            if stat_rows:
+                ops.bn_sums_from_partials(ctx.bn_partials(i, stat_rows, C), stat_rows, C, sums)
+            else:
+                ops.bn_stats(tgt, M, C, sums, self.workspace(ops.bn_workspace_bytes(M, C)))
+            dist.all_reduce_sum_(sums)
+            # finalize + apply in one launch: with the statistics out of the conv's epilogue the chain around the
+            # exchange is two launches per layer (partials -> sums, this)
+            ops.bn_finalize_apply(sums, M * dist.world_size(), tgt, out, M, C, **train)
+        elif stat_rows:
+            ops.bn_train_fwd_partials(ctx.bn_partials(i, stat_rows, C), stat_rows, tgt, out, M, C, **train)
+        else:
+            ops.bn_train_fwd(tgt, out, M, C, ws=self.workspace(ops.bn_workspace_bytes(M, C)), **train)
 
     @staticmethod
     def _resample(st, x, y):
@@ -441,7 +497,7 @@ class Net:
             ops.pool2x_sum(x, y, 0.25)
 
     def predict(self, x, training=False):
-        B = int(x.shape[0])
+        B = x.size(0)
         ctx = self.context(B, "predict")
         x = x.to(self.device, torch.float32).contiguous()
         return self.forward(ctx, x, training=training, seed=np.random.randint(1 << 30)).clone()
@@ -457,185 +513,169 @@ class Net:
         data-gradient + blur^T) for those samples only -- the merged critic pass wants weights from [fakes; reals] and the
         image gradient of x-hat.  ``defer_conv_dw``: the conv filter gradients are left to ``gp_second_order_merged`` (bias
         and Dense gradients are still taken here)."""
-        st_ = self.store
         if need_dw:
-            st_.ensure_opt_state()
-        B = ctx.B
-        WB = B if dw_rows is None else int(dw_rows)
+            self.store.ensure_opt_state()
+        p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active())
         g, g_is_dz = dout, False
-        sync_bn = self.sync_bn and dist.collectives_active()
-        pending_stats = None        # SyncBN: the all-reduce of the NEXT (lower) stage's backward statistics, in flight
-        deferred_ready = []         # SyncBN overlap: gradient slices finished but not yet handed to the reducer (see weight_grads)
         for i in range(len(self.stages) - 1, -1, -1):
             st = self.stages[i]
-            gv = g.view(B, *st.out_shape)
-            # ---- through activation / BN -> gradient w.r.t. the linear op's output
-            if st.bn is not None:
-                C = st.out_shape[-1]
-                M = gv.numel() // C
-                dz = ctx.buf(ctx.dz, i)
-                ws = self.workspace(ops._lib.load().bg_bn_workspace_bytes(M, C))
-                dg = st_.grad_of(st.bn, "gamma") if need_dw else ctx.bn_sums(("dgamma_scratch", i), C)[:C]
-                db = st_.grad_of(st.bn, "beta") if need_dw else ctx.bn_sums(("dbeta_scratch", i), C)[:C]
-                if sync_bn:
-                    world = dist.world_size()
-                    sums = ctx.bn_sums(i, C)
-                    if pending_stats is None:       # last stage: nothing above it to overlap with
-                        ops.bn_bwd_stats(gv, None, ctx.z[i], M, C, ctx.mean[i], ctx.inv[i], sums, ws, lrelu_alpha=st.alpha,
-                                         gamma=st.bn.vars["gamma"], beta=st.bn.vars["beta"])
-                        pending_stats = dist.all_reduce_sum_async(sums)
-                    pending_stats.wait()            # issued before the filter gradient of the stage above: it travelled meanwhile
-                    pending_stats = None
-                    ops.bn_bwd_apply(gv, None, ctx.z[i], dz, M, M * world, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], sums,
-                                     lrelu_alpha=st.alpha, beta=st.bn.vars["beta"])
-                    if need_dw:     # the sums are already global: pre-divide so the flat gradient SUM all-reduce restores them
-                        ops.bn_param_grads(sums, C, 1.0 / world, dg, db)
-                else:
-                    ops.bn_train_bwd(gv, None, ctx.z[i], dz, M, C, st.bn.vars["gamma"], ctx.mean[i], ctx.inv[i], dg, db, ws,
-                                     lrelu_alpha=st.alpha, beta=st.bn.vars["beta"])
-            elif st.act == "lrelu":
-                if g_is_dz:
-                    dz = gv
-                else:
-                    keep = ctx.keep[i] if (st.drop and ctx.dropout_active) else None
-                    dzb = ctx.buf(ctx.dz, i)
-                    if keep is not None and ctx.drop_rows < B:      # masked rows first, the unmasked tail separately
-                        DR = ctx.drop_rows
-                        ops.mul_grad(gv[:DR], ctx.a[i][:DR], dzb[:DR], keep=keep, alpha=st.alpha, scale=1.0 / (1.0 - st.drop))
-                        ops.mul_grad(gv[DR:], ctx.a[i][DR:], dzb[DR:], keep=None, alpha=st.alpha, scale=1.0)
-                        dz = dzb
-                    else:
-                        dz = ops.mul_grad(gv, ctx.a[i], dzb, keep=keep, alpha=st.alpha,
-                                          scale=1.0 / (1.0 - st.drop) if (st.drop and ctx.dropout_active) else 1.0)
-            elif st.act == "tanh":
-                dz = ops.tanh_bwd(gv, ctx.a[i], ctx.buf(ctx.dz, i))
-            else:
-                dz = gv
-            ctx.dz[i] = dz
-            xin = ctx.xin[i]
-            lin = st.lin
             prev = self.stages[i - 1] if i > 0 else None
-
-            def weight_grads(defer_ready=False):
-                dW = st_.grad_of(lin, "kernel")
-                xw, dzw = (xin, dz) if WB == B else (xin[:WB], dz.view(B, *st.out_shape)[:WB])
-                if st.kind == "dense":
-                    K, N = st.in_shape[0], st.out_shape[0]
-                    ops.gemm(xw, dzw, dW, K, N, WB, transA=True, beta=beta, scale=scale)
-                    rows = WB
-                elif st.kind == "conv":
-                    if not defer_conv_dw:
-                        Bc, H, W, Ci = xw.shape
-                        nb = ops.conv2d_bwd_filter_workspace_bytes(Bc, H, W, Ci, lin.filters, lin.k, lin.stride)
-                        ops.conv2d_bwd_filter(xw, dzw, dW, lin.k, lin.stride, beta, scale, self.workspace(nb) if nb else None)
-                    rows = dzw.numel() // lin.filters
-                else:
-                    Bc, H, W, Ci = dzw.shape          # conv input side == ConvT output
-                    nb = ops.conv2d_bwd_filter_workspace_bytes(Bc, H, W, Ci, xw.shape[3], lin.k, lin.stride)
-                    ops.conv2d_bwd_filter(dzw, xw, dW, lin.k, lin.stride, beta, scale, self.workspace(nb) if nb else None)
-                    rows = dzw.numel() // lin.filters
-                if "bias" in lin.vars:
-                    N = st.out_shape[-1]
-                    ws = self.workspace(ops.colsum_workspace_bytes(rows, N))
-                    ops.colsum(dzw, st_.grad_of(lin, "bias"), rows, N, ws, beta=beta, scale=scale)
-                if reducer is not None and not (defer_conv_dw and st.kind == "conv"):
-                    # Under the SyncBN overlap a slice is NOT handed over right away: ready() may flush a 16 MB bucket onto the
-                    # collective stream, and the small statistics exchange of the next stage down, issued one iteration later,
-                    # would queue behind it -- back on the critical path.  The slice waits until that exchange is in flight.
-                    if defer_ready:
-                        deferred_ready.append(st_.train_range(lin, st.bn))
-                    else:
-                        reducer.ready(*st_.train_range(lin, st.bn))
-
+            has_dw = need_dw and st.kind not in RESAMPLE
+            dz = ctx.dz[i] = self._grad_through_activation(p, i, st, g.view(ctx.B, *st.out_shape), g_is_dz)
             # SyncBN with a BatchNorm stage below: the data gradient goes FIRST, the lower stage's backward statistics are
             # reduced and their all-reduce is put in flight, and only then this stage's filter gradient runs -- the small
             # latency-bound collective hides behind an MFMA kernel instead of sitting on the critical path of every layer.
             # (The filter gradient's split-K workspace and the statistics' partials share net.workspace(): the statistics
             # kernel has finished with it before the filter gradient is enqueued on the same stream.)
-            overlap = sync_bn and need_dw and prev is not None and prev.bn is not None and st.kind not in RESAMPLE
-            if need_dw and not overlap and st.kind not in RESAMPLE:
-                weight_grads()
-            # ---- input gradient
+            overlap = has_dw and p.sync_bn and prev is not None and prev.bn is not None
+            if has_dw and not overlap:
+                self._weight_grads(p, i, st, dz)
             if i == 0 and not need_dx:
-                if reducer is not None:
-                    for rng in deferred_ready:
-                        reducer.ready(*rng)
+                p.release_deferred()
                 return None
-            fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
-            tgt = ctx.buf(ctx.dz, i - 1).view(B, *st.in_shape) if i > 0 else ctx.input_grad().view(B, *st.in_shape)
-            if st.kind == "upsample":         # transpose of the upsample; the stage below applies its own BN / activation backward
-                ops.pool2x_sum(dz.view(B, *st.out_shape), tgt, 1.0)
-                g, g_is_dz = tgt, False
-                continue
-            if st.kind == "avgpool":
-                dzp = dz.view(B, *st.out_shape)
-                if not fuse:
-                    ops.upsample2x(dzp, tgt, 0.25)
-                else:       # lands as the dz of the conv + LeakyReLU (+ Dropout) stage below: one launch instead of upsample + mul_grad
-                    pk = ctx.keep[i - 1] if (prev.drop and ctx.dropout_active) else None
-                    ref = ctx.a[i - 1]
-                    if pk is not None and ctx.drop_rows < B:        # masked rows first, the unmasked tail separately
-                        DR = ctx.drop_rows
-                        ops.upsample2x(dzp[:DR], tgt[:DR], 0.25, ref=ref[:DR], keep=pk, alpha=prev.alpha, grad_scale=1.0 / (1.0 - prev.drop))
-                        ops.upsample2x(dzp[DR:], tgt[DR:], 0.25, ref=ref[DR:], alpha=prev.alpha)
-                    else:
-                        ops.upsample2x(dzp, tgt, 0.25, ref=ref, keep=pk, alpha=prev.alpha,
-                                       grad_scale=1.0 / (1.0 - prev.drop) if pk is not None else 1.0)
-                g, g_is_dz = tgt, fuse
-                continue
-            Bx = B
-            dzx = dz
-            if i == 0 and dx_rows is not None:        # the image gradient is wanted for samples [lo, hi) only
-                lo, hi = dx_rows
-                dzx = dz.view(B, *st.out_shape)[lo:hi]
-                tgt = tgt[lo:hi]
-                Bx = hi - lo
-            epi = None
-            if st.kind != "dense":
-                if st.kind == "conv":
-                    geom = (True, Bx, st.in_shape[0], st.in_shape[1], st.in_shape[2], lin.filters, lin.k, lin.stride)
-                else:
-                    geom = (False, Bx, st.out_shape[0], st.out_shape[1], lin.filters, st.in_shape[2], lin.k, lin.stride)
-                if fuse:
-                    pk = ctx.keep[i - 1] if (prev.drop and ctx.dropout_active) else None
-                    epi = self._epi(*geom, EPI_MUL_GRAD, ref=ctx.a[i - 1], keep=pk, alpha=prev.alpha,
-                                    scale=1.0 / (1.0 - prev.drop) if pk is not None else 1.0,
-                                    keep_elems=ctx.keep_elems(i - 1) if pk is not None else 0)
-                else:
-                    epi = self._epi(*geom, EPI_NONE)
-            if st.kind == "dense":
-                K, N = st.in_shape[0], st.out_shape[0]
-                ops.gemm(dzx, lin.vars["kernel"], tgt, Bx, K, N, transB=True)
-            elif st.kind == "conv":
-                ops.conv2d_bwd_data(dzx, lin.vars["kernel"], tgt, lin.k, lin.stride, epi, math=self.conv_math)
-            else:
-                ops.conv2d_fwd(dzx, self.store.transposed_kernel(lin), tgt, lin.k, lin.stride, epi, math=self.conv_math)
+            g, g_is_dz = self._input_grad(p, i, st, prev, dz, dx_rows)
             if overlap:
-                Cp = prev.out_shape[-1]
-                gp = tgt.view(B, *prev.out_shape)
-                Mp = gp.numel() // Cp
-                sums = ctx.bn_sums(i - 1, Cp)
-                ops.bn_bwd_stats(gp, None, ctx.z[i - 1], Mp, Cp, ctx.mean[i - 1], ctx.inv[i - 1], sums,
-                                 self.workspace(ops._lib.load().bg_bn_workspace_bytes(Mp, Cp)), lrelu_alpha=prev.alpha,
-                                 gamma=prev.bn.vars["gamma"], beta=prev.bn.vars["beta"])
-                pending_stats = dist.all_reduce_sum_async(sums)
-                if reducer is not None:             # slices finished before this exchange was issued may go out behind it now
-                    for rng in deferred_ready:
-                        reducer.ready(*rng)
-                    deferred_ready.clear()
-                weight_grads(defer_ready=True)
-            g, g_is_dz = tgt, fuse
-        if reducer is not None:
-            for rng in deferred_ready:
-                reducer.ready(*rng)
-        din = g
+                self._bn_bwd_stats(p, i - 1, prev, g)
+                p.release_deferred()        # slices finished before this exchange was issued may go out behind it now
+                self._weight_grads(p, i, st, dz, defer_ready=True)
+        p.release_deferred()
         if self.blur is not None:
             # forward's blurred input is dead by now; reuse it for blur^T(din)
             out = ctx.a0 if dx_rows is None else ctx.a0[dx_rows[0]:dx_rows[1]]
-            return self.apply_blur(din.view(din.shape[0], *self.in_shape), out)
-        return din
+            return self.apply_blur(g.view(g.shape[0], *self.in_shape), out)
+        return g
+
+    def _grad_through_activation(self, p, i, st, gv, g_is_dz):
+        """Through stage i's activation / BatchNorm: the gradient w.r.t. its linear op's output.  ``g_is_dz``: the launch that
+        produced ``gv`` has applied LeakyReLU' / Dropout' already."""
+        ctx = p.ctx
+        if st.bn is not None:
+            return self._bn_backward(p, i, st, gv)
+        if st.act == "tanh":
+            return ops.tanh_bwd(gv, ctx.a[i], ctx.buf(ctx.dz, i))
+        if st.act != "lrelu" or g_is_dz:
+            return gv
+        dz, a = ctx.buf(ctx.dz, i), ctx.a[i]
+        ctx.masked_then_tail(i, lambda rows, keep, scale: ops.mul_grad(gv[rows], a[rows], dz[rows], keep=keep, alpha=st.alpha, scale=scale))
+        return dz
+
+    def _bn_backward(self, p, i, st, gv):
+        ctx = p.ctx
+        C = st.out_shape[-1]
+        M = gv.numel() // C
+        dz = ctx.buf(ctx.dz, i)
+        dg, db = (self.store.grad_of(st.bn, "gamma"), self.store.grad_of(st.bn, "beta")) if p.need_dw else ctx.bn_grad_scratch(i, C)
+        gamma, beta = st.bn.vars["gamma"], st.bn.vars["beta"]
+        if not p.sync_bn:
+            ops.bn_train_bwd(gv, None, ctx.z[i], dz, M, C, gamma, ctx.mean[i], ctx.inv[i], dg, db,
+                             self.workspace(ops.bn_workspace_bytes(M, C)), lrelu_alpha=st.alpha, beta=beta)
+            return dz
+        world = dist.world_size()
+        if p.pending_stats is None:         # nothing above it to overlap with (the last stage, or no filter gradient there)
+            self._bn_bwd_stats(p, i, st, gv)
+        p.pending_stats.wait()              # issued before the filter gradient of the stage above: it travelled meanwhile
+        p.pending_stats = None
+        sums = ctx.bn_sums(i, C)
+        ops.bn_bwd_apply(gv, None, ctx.z[i], dz, M, M * world, C, gamma, ctx.mean[i], ctx.inv[i], sums, lrelu_alpha=st.alpha, beta=beta)
+        if p.need_dw:       # the sums are already global: pre-divide so the flat gradient SUM all-reduce restores them
+            ops.bn_param_grads(sums, C, 1.0 / world, dg, db)
+        return dz
+
+    def _bn_bwd_stats(self, p, i, st, g):
+        """SyncBN: the backward statistics of BatchNorm stage i from the gradient ``g`` of its output, their all-reduce in flight."""
+        ctx = p.ctx
+        C = st.out_shape[-1]
+        gv = g.view(ctx.B, *st.out_shape)
+        M = gv.numel() // C
+        sums = ctx.bn_sums(i, C)
+        ops.bn_bwd_stats(gv, None, ctx.z[i], M, C, ctx.mean[i], ctx.inv[i], sums, self.workspace(ops.bn_workspace_bytes(M, C)),
+                         lrelu_alpha=st.alpha, gamma=st.bn.vars["gamma"], beta=st.bn.vars["beta"])
+        p.pending_stats = dist.all_reduce_sum_async(sums)
+
+    def _weight_grads(self, p, i, st, dz, defer_ready=False):
+        """Kernel and bias gradients of stage i from the pass's first dw_rows samples; its slice of the flat buffer to the reducer."""
+        B, WB, lin = p.ctx.B, p.dw_rows, st.lin
+        xin = p.ctx.xin[i]
+        xw, dzw = (xin, dz) if WB == B else (xin[:WB], dz.view(B, *st.out_shape)[:WB])
+        deferred = p.defer_conv_dw and st.kind == "conv"        # left to gp_second_order_merged, the reducer's hand-over too
+        if st.kind == "dense":
+            ops.gemm(xw, dzw, self.store.grad_of(lin, "kernel"), st.in_shape[0], st.out_shape[0], WB, transA=True, beta=p.beta, scale=p.scale)
+        elif not deferred:
+            self._filter_grad(st, xw, dzw, p.beta, p.scale)
+        if "bias" in lin.vars:
+            N = st.out_shape[-1]
+            rows = dzw.numel() // N
+            ops.colsum(dzw, self.store.grad_of(lin, "bias"), rows, N, self.workspace(ops.colsum_workspace_bytes(rows, N)), beta=p.beta, scale=p.scale)
+        if p.reducer is not None and not deferred:
+            # Under the SyncBN overlap a slice is NOT handed over right away: ready() may flush a 16 MB bucket onto the
+            # collective stream, and the small statistics exchange of the next stage down, issued one iteration later,
+            # would queue behind it -- back on the critical path.  The slice waits until that exchange is in flight.
+            if defer_ready:
+                p.deferred_ready.append(self.store.train_range(lin, st.bn))
+            else:
+                p.reducer.ready(*self.store.train_range(lin, st.bn))
+
+    def _input_grad(self, p, i, st, prev, dz, dx_rows):
+        """The gradient w.r.t. stage i's input into the dz buffer of the stage below (the pass's input-gradient buffer at i = 0).
+        Returns (it, whether it is already that stage's dz: LeakyReLU' / Dropout' of a conv + LeakyReLU stage below ride in
+        the data gradient's epilogue or in the pooling backward)."""
+        ctx = p.ctx
+        fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
+        tgt = (ctx.buf(ctx.dz, i - 1) if i > 0 else ctx.input_grad()).view(ctx.B, *st.in_shape)
+        if st.kind == "upsample":           # transpose of the upsample
+            ops.pool2x_sum(dz.view(ctx.B, *st.out_shape), tgt, 1.0)
+        elif st.kind == "avgpool" and not fuse:
+            ops.upsample2x(dz.view(ctx.B, *st.out_shape), tgt, 0.25)
+        elif st.kind == "avgpool":          # one launch instead of upsample + mul_grad
+            dzp, ref = dz.view(ctx.B, *st.out_shape), ctx.a[i - 1]
+            ctx.masked_then_tail(i - 1, lambda rows, keep, scale: ops.upsample2x(dzp[rows], tgt[rows], 0.25, ref=ref[rows], keep=keep,
+                                                                                alpha=prev.alpha, grad_scale=scale))
+        else:
+            if i == 0 and dx_rows is not None:        # the image gradient is wanted for samples [lo, hi) only
+                lo, hi = dx_rows
+                dz, tgt = dz.view(ctx.B, *st.out_shape)[lo:hi], tgt[lo:hi]
+            if st.kind == "dense":
+                ops.gemm(dz, st.lin.vars["kernel"], tgt, tgt.size(0), st.in_shape[0], st.out_shape[0], transB=True)
+            elif fuse:
+                keep, scale, keep_elems = ctx.dropout(i - 1)
+                self._conv(st, dz, tgt, True, EPI_MUL_GRAD, ref=ctx.a[i - 1], keep=keep, alpha=prev.alpha, scale=scale, keep_elems=keep_elems)
+            else:
+                self._conv(st, dz, tgt, True, EPI_NONE)
+        return tgt, fuse
 
     # ------------------------------------------------------------------ GP second order
+    def _gp_kinds(self):
+        """What the linearised forward of the gradient penalty does per stage; refuses any but the reference critic shape."""
+        kinds = []
+        for i, st in enumerate(self.stages):
+            last = i == len(self.stages) - 1
+            if st.kind == "conv" and st.fusable_grad and not last:
+                kinds.append("conv")
+            elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
+                kinds.append("dense")
+            elif st.kind in RESAMPLE and not last:
+                kinds.append("resample")
+            else:
+                raise NotImplementedError(_GP_SHAPE_MESSAGE)
+        return kinds
+
+    def _gp_stage(self, kind, st, wx, wdz, wbeta, v, ref, vout, reducer):
+        """One stage of the penalty's second order: the filter gradient wgrad(wx, wdz) into store.grad (beta = ``wbeta``), then the
+        linearised forward vout = op(v) with the LeakyReLU signs of ``ref`` frozen.  The Dense(1) head's is the column sum of v."""
+        if kind == "resample":
+            self._resample(st, v, vout)
+            return
+        if kind == "conv":
+            self._filter_grad(st, wx, wdz, wbeta, 1.0)
+        else:
+            n, K = v.size(0), st.in_shape[0]
+            ws = self.workspace(ops.colsum_workspace_bytes(n, K))
+            ops.colsum(v.reshape(n, K), self.store.grad_of(st.lin, "kernel").view(K), n, K, ws, beta=1.0, scale=1.0)
+        if reducer is not None:     # this layer's gradient (first-order pass + this wgrad) is complete
+            reducer.ready(*self.store.train_range(st.lin, st.bn))
+        if kind == "conv":
+            self._conv(st, v, vout, False, EPI_MUL_GRAD, ref=ref, alpha=st.alpha)
+
     def gp_second_order_merged(self, ctx: Context, lo, hi, reducer=None):
         """The second order of the penalty AND the filter gradients of the whole merged critic pass, one launch per layer.
 
@@ -646,69 +686,23 @@ class Net:
         place -- both are ONE filter gradient over all 3B rows of (a_{i-1}, dz_i): five launches (and their slab reduces)
         fewer per D-step, and the remaining ones run at 3B rows instead of 2B + B.  The caller has put delta-bar_0 into
         ctx.a0[lo:hi] and run ``backward(..., defer_conv_dw=True)``."""
-        st_ = self.store
-        st_.ensure_opt_state()
-        B3, Bh = ctx.B, hi - lo
-        for i, st in enumerate(self.stages):
-            lin = st.lin
-            last = i == len(self.stages) - 1
-            if st.kind == "conv" and st.fusable_grad and not last:
-                xin = ctx.xin[i]                                  # [3B, ...]: activations of [fakes; reals], delta-bar_{i-1} in the x-hat rows
-                _, H, W, Ci = xin.shape
-                nb = ops.conv2d_bwd_filter_workspace_bytes(B3, H, W, Ci, lin.filters, lin.k, lin.stride)
-                ops.conv2d_bwd_filter(xin, ctx.dz[i].view(B3, *st.out_shape), st_.grad_of(lin, "kernel"), lin.k, lin.stride, 0.0, 1.0,
-                                      self.workspace(nb) if nb else None)
-                if reducer is not None:
-                    reducer.ready(*st_.train_range(lin, st.bn))
-                ah = ctx.a[i][lo:hi]
-                if self.capture_branches is not None:            # test instrumentation: the signs about to be overwritten
-                    self.capture_branches.append((ah > 0).cpu().numpy())
-                epi = self._epi(False, Bh, H, W, Ci, lin.filters, lin.k, lin.stride, EPI_MUL_GRAD, ref=ah, alpha=st.alpha)
-                ops.conv2d_fwd(xin[lo:hi], self.store.transposed_kernel(lin), ah, lin.k, lin.stride, epi, math=self.conv_math)   # in place: ref == out
-            elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
-                K = st.in_shape[0]
-                ws = self.workspace(ops.colsum_workspace_bytes(Bh, K))
-                ops.colsum(ctx.xin[i][lo:hi].reshape(Bh, K), st_.grad_of(lin, "kernel").view(K), Bh, K, ws, beta=1.0, scale=1.0)
-                if reducer is not None:
-                    reducer.ready(*st_.train_range(lin, st.bn))
-            elif st.kind in RESAMPLE and not last:
-                # delta-bar_i = op(delta-bar_{i-1}): from the x-hat rows of a_{i-1} into those of a_i (dead after the backward)
-                self._resample(st, ctx.xin[i][lo:hi], ctx.a[i][lo:hi])
-            else:
-                raise NotImplementedError(_GP_SHAPE_MESSAGE)
+        kinds = self._gp_kinds()
+        self.store.ensure_opt_state()
+        for i, (kind, st) in enumerate(zip(kinds, self.stages)):
+            xin = ctx.xin[i]                # [3B, ...]: activations of [fakes; reals], delta-bar_{i-1} in the x-hat rows
+            ah = ctx.a[i][lo:hi]            # delta-bar_i goes where the x-hat rows of a_i are: in place, ref == out
+            if self.capture_branches is not None and kind == "conv":      # test instrumentation: the signs about to be overwritten
+                self.capture_branches.append((ah > 0).cpu().numpy())
+            self._gp_stage(kind, st, xin, ctx.dz[i], 0.0, xin[lo:hi], ah, ah, reducer)
 
     def gp_second_order(self, ctx: Context, v0, reducer=None):
         """SURVEY.md 8a, GP derivation step 2: one linearised forward of the critic on ``v0`` with the
         LeakyReLU masks of the x-hat pass frozen, plus one wgrad per conv layer against the zeta_i kept by
         the first-order backward (``ctx.dz``); accumulates into ``store.grad`` (beta = 1)."""
-        st_ = self.store
-        st_.ensure_opt_state()
-        B = ctx.B
+        kinds = self._gp_kinds()
+        self.store.ensure_opt_state()
         v = v0
-        for i, st in enumerate(self.stages):
-            lin = st.lin
-            last = i == len(self.stages) - 1
-            if st.kind == "conv" and st.fusable_grad and not last:
-                vin = v.view(B, *st.in_shape)
-                Bc, H, W, Ci = vin.shape
-                nb = ops.conv2d_bwd_filter_workspace_bytes(Bc, H, W, Ci, lin.filters, lin.k, lin.stride)
-                ops.conv2d_bwd_filter(vin, ctx.dz[i], st_.grad_of(lin, "kernel"), lin.k, lin.stride, 1.0, 1.0,
-                                      self.workspace(nb) if nb else None)
-                vo = ctx.buf(ctx.v, i)
-                epi = self._epi(False, Bc, H, W, Ci, lin.filters, lin.k, lin.stride, EPI_MUL_GRAD, ref=ctx.a[i], alpha=st.alpha)
-                if reducer is not None:     # this layer's gradient (first-order pass + this wgrad) is complete
-                    reducer.ready(*st_.train_range(lin, st.bn))
-                ops.conv2d_fwd(vin, self.store.transposed_kernel(lin), vo, lin.k, lin.stride, epi, math=self.conv_math)
-                v = vo
-            elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
-                K = st.in_shape[0]
-                ws = self.workspace(ops.colsum_workspace_bytes(B, K))
-                ops.colsum(v.view(B, K), st_.grad_of(lin, "kernel").view(K), B, K, ws, beta=1.0, scale=1.0)
-                if reducer is not None:
-                    reducer.ready(*st_.train_range(lin, st.bn))
-            elif st.kind in RESAMPLE and not last:
-                vo = ctx.buf(ctx.v, i)
-                self._resample(st, v.view(B, *st.in_shape), vo)
-                v = vo
-            else:
-                raise NotImplementedError(_GP_SHAPE_MESSAGE)
+        for i, (kind, st) in enumerate(zip(kinds, self.stages)):
+            vin = v.view(ctx.B, *st.in_shape)
+            v = None if kind == "dense" else ctx.buf(ctx.v, i)
+            self._gp_stage(kind, st, vin, ctx.dz[i], 1.0, vin, ctx.a[i], v, reducer)

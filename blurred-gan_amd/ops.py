@@ -235,6 +235,10 @@ def colsum(x, out, M, N, ws, square=False, beta=0.0, scale=1.0):
     return out
 
 
+def bn_workspace_bytes(M, Cc):
+    return _lib.load().bg_bn_workspace_bytes(M, Cc)
+
+
 def bn_train_fwd(x, y, M, Cc, gamma, beta, moving_mean, moving_var, save_mean, save_inv, ws, eps=1e-3, momentum=0.99,
                  unbiased=True, lrelu_alpha=LRELU_ALPHA):
     _f32(x, y, gamma, beta, save_mean, save_inv)

@@ -430,12 +430,10 @@ class WGAN:
             # the backward do not depend on the penalty (d loss / d scores is +-1/gbs and the drift term), so the x-hat rows
             # ride along with seed 1 and come out as the zeta_i the second-order pass needs; weight gradients use rows [0, 2B),
             # the image gradient is taken for rows [2B, 3B) only.
-            a = self._inj("alpha")
-            a = self._as_device(a).view(B) if a is not None else self._uniform("alpha", (B,))
             c3 = D.context(3 * B, "fr3", drop_rows=2 * B)
             # x-hat = reals + a (fakes - reals) (wgan.py:239) joins the batch inside forward: behind the blur it is formed on the fly
             # by the one launch that blurs all three slices (bg_blur3_lerp_nhwc_f32), else bg_lerp_f32 writes it to the buffer
-            s3 = D.forward(c3, [fakes, reals], training=True, masks=masks, seed=seed, lerp_alpha=a,
+            s3 = D.forward(c3, [fakes, reals], training=True, masks=masks, seed=seed, lerp_alpha=self._gp_alpha(B),
                            lerp_out=self._buf("xhat", tuple(reals.shape))).view(3 * B)
             fs, rs = s3[:B], s3[B:2 * B]
             ds3 = self._buf("ds3", (3 * B,))
@@ -446,21 +444,13 @@ class WGAN:
                            dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad)
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
             ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
-            coef = vs * float(hp.gp_coefficient) * 2.0 / float(B * dist.world_size())
             if one_wgrad:
                 # delta-bar_0 goes into the x-hat rows of the pass's (blurred) input buffer, where the layer-1 filter gradient
                 # reads it beside the activations of [fakes; reals]; g itself lives in those rows and is dead after the seed
-                hat0 = c3.a0[2 * B:3 * B]
-                if D.blur is not None:
-                    gbar = ops.gp_seed(g, norms, coef, self._buf("gbar", tuple(g.shape)), self.gp_zero_norm_guard)
-                    D.apply_blur(gbar, hat0)
-                else:
-                    ops.gp_seed(g, norms, coef, hat0.view(g.shape), self.gp_zero_norm_guard)      # g is the net's own input-gradient buffer
+                self._gp_v0(D, g, norms, out=c3.a0[2 * B:3 * B])
                 D.gp_second_order_merged(c3, 2 * B, 3 * B, reducer=red)
             else:
-                gbar = ops.gp_seed(g, norms, coef, self._buf("gbar", tuple(g.shape)), self.gp_zero_norm_guard)
-                v0 = D.apply_blur(gbar, self._buf("v0", tuple(g.shape))) if D.blur is not None else gbar
-                D.gp_second_order(c3.rows(2 * B, 3 * B), v0, reducer=red)
+                D.gp_second_order(c3.rows(2 * B, 3 * B), self._gp_v0(D, g, norms), reducer=red)
         else:
             cfr = D.context(2 * B, "fr")
             s2 = D.forward(cfr, [fakes, reals], training=True, masks=masks, seed=seed).view(2 * B)
@@ -473,12 +463,7 @@ class WGAN:
             D.backward(cfr, ds2.view(2 * B, 1), need_dx=False, need_dw=True, beta=0.0, scale=1.0,
                        reducer=None if self.uses_gradient_penalty else red)
             if self.uses_gradient_penalty:
-                # d/dW of vec_scale * gp_coefficient * mean_global((n-1)^2): seed carries the whole factor
-                coef = vs * float(hp.gp_coefficient) * 2.0 / float(B * dist.world_size())
-                gbar = ops.gp_seed(g, norms, coef, self._buf("gbar", tuple(g.shape)), self.gp_zero_norm_guard)
-                chat = D.context(B, "hat")
-                v0 = D.apply_blur(gbar, self._buf("v0", tuple(g.shape))) if D.blur is not None else gbar
-                D.gp_second_order(chat, v0, reducer=red)
+                D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms), reducer=red)
         red.finish()
         optimizers.get_optimizer(self.discriminator).apply(store)
         disc_loss = None              # inside train_on_batch the value is read with the rest of the step's metrics
@@ -497,20 +482,31 @@ class WGAN:
             a = torch.from_numpy(a)
         return a.to(torch.uint8)
 
+    def _gp_alpha(self, B):
+        """The interpolation weights of x-hat (wgan.py:237): injected, or drawn."""
+        a = self._inj("alpha")
+        return self._as_device(a).view(B) if a is not None else self._uniform("alpha", (B,))
+
+    def _gp_coef(self, B):
+        """d/dW of vec_scale * gp_coefficient * mean_global((n-1)^2): the second order's seed carries the whole factor."""
+        return self._vec_scale(B) * float(self.hparams.gp_coefficient) * 2.0 / float(B * dist.world_size())
+
+    def _gp_v0(self, D, g, norms, out=None):
+        """The second order's input delta-bar_0: the seed of the image gradient ``g``, through the blur where the critic has one.
+        Lands in ``out`` (the x-hat rows of the merged pass's input buffer) or in a buffer of the model's own."""
+        own = lambda name: self._buf(name, tuple(g.shape))
+        coef = self._gp_coef(int(g.shape[0]))
+        if D.blur is None:      # with ``out``, g is the net's own input-gradient buffer
+            return ops.gp_seed(g, norms, coef, own("gbar") if out is None else out.view(g.shape), self.gp_zero_norm_guard)
+        gbar = ops.gp_seed(g, norms, coef, own("gbar"), self.gp_zero_norm_guard)
+        return D.apply_blur(gbar, own("v0") if out is None else out)
+
     def _gp_first_order(self, reals, fakes):
-        """wgan.py:234-245 on the device: x_hat, critic forward (training=False), gradient w.r.t. x_hat
-        (through blur^T), per-sample L2 norms.  Leaves zeta_i in the 'hat' context for the second order."""
+        """Leaves zeta_i in the 'hat' context for the second order."""
         B = int(reals.shape[0])
         D = self.discriminator.net()
-        a = self._inj("alpha")
-        a = self._as_device(a).view(B) if a is not None else self._uniform("alpha", (B,))
-        xhat = ops.lerp(reals, fakes, a, self._buf("xhat", tuple(reals.shape)))
-        chat = D.context(B, "hat")
-        D.forward(chat, xhat, training=False)
-        ones = ops.fill(self._buf("ones", (B, 1)), 1.0)
-        g = D.backward(chat, ones, need_dx=True, need_dw=False)
-        norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
-        return norms, g
+        return _first_order(D, D.context(B, "hat"), reals, fakes, self._gp_alpha(B), self._buf("xhat", tuple(reals.shape)),
+                            self._buf("ones", (B, 1)), self._buf("gp_norms", (B,)))
 
     # ---- generator
     def generator_loss(self, fake_scores):
@@ -640,6 +636,14 @@ class WGAN:
         return history
 
 
+def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms):
+    """wgan.py:234-245 on the device: x_hat, critic forward (training=False), gradient w.r.t. x_hat (through blur^T),
+    per-sample L2 norms.  ``xhat``, ``ones`` and ``norms`` are the caller's buffers; returns (norms, gradient)."""
+    D.forward(ctx, ops.lerp(reals, fakes, alpha, xhat), training=False)
+    g = D.backward(ctx, ops.fill(ones, 1.0), need_dx=True, need_dw=False)
+    return ops.row_norm(g, norms), g
+
+
 def gradient_penalty(discriminator, reals, fakes, alpha=None):
     """wgan.py:234-246 (value only): mean((||d D(x_hat)/d x_hat|| - 1)^2) on the HIP kernels."""
     D = discriminator.net()
@@ -649,11 +653,9 @@ def gradient_penalty(discriminator, reals, fakes, alpha=None):
     B = int(reals.shape[0])
     if alpha is None:
         alpha = ops.uniform(torch.empty(B, dtype=torch.float32, device=dev), get_seed() + 17, np.random.randint(1 << 30))
-    xhat = ops.lerp(reals, fakes, alpha.to(dev, torch.float32).contiguous().view(B), torch.empty_like(reals))
-    ctx = D.context(B, "gp_fn")
-    D.forward(ctx, xhat, training=False)
-    g = D.backward(ctx, ops.fill(torch.empty(B, 1, dtype=torch.float32, device=dev), 1.0), need_dx=True, need_dw=False)
-    n = ops.row_norm(g, torch.empty(B, dtype=torch.float32, device=dev))
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    n, _ = _first_order(D, D.context(B, "gp_fn"), reals, fakes, alpha.to(dev, torch.float32).contiguous().view(B), torch.empty_like(reals),
+                        new(B, 1), new(B))
     # mean((n - 1)^2) by the loss kernel itself (metric slot 5 of bg_wgangp_d_loss), not by torch arithmetic
     zero = ops.fill(torch.empty(B, dtype=torch.float32, device=dev), 0.0)
     scratch, met = torch.empty(2, B, dtype=torch.float32, device=dev), torch.empty(8, dtype=torch.float32, device=dev)
