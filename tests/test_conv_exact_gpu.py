@@ -12,8 +12,9 @@ case names the (tap, ci, co) or the dy pixel its first wrong output came from.
 The fallbacks behind the once-read switches that take a 5x5-only fast path away (conv_cases.SWITCHED_ENV) run in ONE fresh child
 process started with them set (tests/conv_switched_child.py); no process that has initialised the GPU replaces its program.
 
-Not here: tanh (inexact; tests/test_conv_gpu.py holds it to a tolerance), bf16x6 (tests/test_conv_math_gpu.py), and the tuning
-aids among the once-read switches (the rest of conv_cases.STATIC_SWITCHES)."""
+Not here: tanh (inexact; tests/test_conv_gpu.py holds it to a tolerance) and the tuning
+aids among the once-read switches (the rest of conv_cases.STATIC_SWITCHES).  The split-bf16 kernel (conv_math="bf16x6") has its own
+exact file, tests/test_conv_x6_exact_gpu.py, which borrows the guarded buffers of this one."""
 import numpy as np
 import pytest
 import torch

@@ -121,7 +121,7 @@ for (B, H, W, Ci, Co, s) in CASES:
     n += any("x6" in k for k in names)
 # the data-gradient direction (no geometry of it is in the table) through the epilogue, Inf / NaN and reproducibility checks
 import test_conv_math_gpu as M
-for mode in ("none_bias", "bias_lrelu_keep", "mul_grad_alias", "tanh", "stats"):
+for mode in ("none_bias", "bias_lrelu_keep", "mul_grad_alias", "tanh", "affine_lrelu", "stats"):
     M.test_epilogues_x6(1, mode)
 M.test_inf_nan_inputs_x6(1)
 M.test_x6_is_bit_reproducible(1)
@@ -143,7 +143,7 @@ def _lrelu(v, a=0.3):
 
 
 @pytest.mark.parametrize("bwd", [0])          # bwd = 1: test_kernel_on_every_geometry_it_runs
-@pytest.mark.parametrize("mode", ["none_bias", "bias_lrelu_keep", "mul_grad_alias", "tanh", "stats"])
+@pytest.mark.parametrize("mode", ["none_bias", "bias_lrelu_keep", "mul_grad_alias", "tanh", "affine_lrelu", "stats"])
 def test_epilogues_x6(bwd, mode):
     from blurred_gan_amd import ops
     B, H, W, Ci, Co = G_EPI
@@ -172,6 +172,9 @@ def test_epilogues_x6(bwd, mode):
         epi, ref = ops.epilogue(ops.EPI_MUL_GRAD, ref=out), acc * np.where(r > 0, 1.0, 0.3)
     elif mode == "tanh":
         epi, ref = ops.epilogue(ops.EPI_TANH, bias=dev(bias)), np.tanh(acc + bias)
+    elif mode == "affine_lrelu":                       # folded inference BatchNorm: per-channel multiplier, then bias, then LeakyReLU
+        mul = rng.uniform(0.5, 1.5, N).astype(np.float32)
+        epi, ref = ops.epilogue(ops.EPI_AFFINE_LRELU, bias=dev(bias), ref=dev(mul)), _lrelu(acc * mul + bias)
     else:
         stats = torch.full((4096 * 2 * N,), 3.0, device="cuda")
         epi, ref = ops.epilogue(ops.EPI_NONE, stats=stats), acc
