@@ -174,3 +174,43 @@ def product_lrelu_branches(gan, B):
         hat = masks(D, c3, 2 * B, 3 * B)
     return {"fake": masks(D, c3, 0, B), "real": masks(D, c3, B, 2 * B), "hat": hat,
             "g": masks(G, G.context(B, "g")), "d_gstep": masks(D, D.context(B, "hat"))}
+
+
+# Guarded device buffers of the exact-data tests: what a kernel writes beyond its tensor, or never writes inside it, shows.
+GUARD = 256
+SENTINEL = {torch.float32: -98765.0, torch.float64: -98765.0, torch.int32: 77, torch.uint8: 0xA5}
+_BITS = {torch.float32: np.uint32, torch.float64: np.uint64, torch.int32: np.int32, torch.uint8: np.uint8}
+_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.uint8: np.uint8}
+
+
+class Guarded:
+    """n elements inside a buffer whose bands on either side hold a finite sentinel.  The view starts `offset` elements past a
+    16-byte boundary (0: aligned; 1 float: misaligned) and holds NaN unless `init` is given (integer types need one)."""
+
+    def __init__(self, n, init=None, dtype=torch.float32, offset=0):
+        self.n, self.dtype, self.lo = int(n), dtype, GUARD + offset
+        self.buf = torch.full((self.n + 2 * GUARD + offset,), SENTINEL[dtype], dtype=dtype, device="cuda")
+        self.view = self.buf[self.lo:self.lo + self.n]
+        assert (self.view.data_ptr() - offset * self.buf.element_size()) % 16 == 0
+        assert (self.view.data_ptr() % 16 == 0) == ((offset * self.buf.element_size()) % 16 == 0)
+        self.init = None
+        if init is None:
+            self.view.fill_(float("nan"))
+        else:
+            self.init = np.ascontiguousarray(init, dtype=_NP[dtype]).ravel()
+            assert self.init.size == self.n
+            self.view.copy_(torch.from_numpy(self.init))
+
+    def guards_intact(self):
+        s = np.array(SENTINEL[self.dtype], _NP[self.dtype]).view(_BITS[self.dtype])
+        lo, hi = (b.cpu().numpy().view(_BITS[self.dtype]) for b in (self.buf[:self.lo], self.buf[self.lo + self.n:]))
+        return bool((lo == s).all() and (hi == s).all())
+
+    def unchanged(self):
+        return np.array_equal(self.view.cpu().numpy().view(_BITS[self.dtype]), self.init.view(_BITS[self.dtype]))
+
+    def get(self, *shape):
+        return self.view.cpu().numpy().reshape(shape or (self.n,))
+
+    def t(self, *shape):
+        return self.view.view(*shape)
