@@ -1,6 +1,7 @@
-"""Case tables, exact integer data, float64 reference and restated host dispatch for the 5x5 convolutions of csrc/conv_igemm.hip,
-csrc/conv_c16.hip, csrc/conv_rows.hip and csrc/conv_wgrad.hip (tests/test_conv_cases_cpu.py checks the tables on the CPU,
-tests/test_conv_exact_gpu.py runs them on the GPU).
+"""Case tables, exact integer data, float64 reference and restated host dispatch for the k x k convolutions of csrc/conv_igemm.hip,
+csrc/conv_c16.hip, csrc/conv_rows.hip and csrc/conv_wgrad.hip.  The tables of this file are the 5x5 ones (tests/test_conv_cases_cpu.py
+checks them on the CPU, tests/test_conv_exact_gpu.py runs them on the GPU); tests/conv_ksize_cases.py holds the tables at k = 3 and 1
+on the same functions.  A case shape is (B, H, W, Cin, Cout, stride) with an optional seventh element k; without it k = 5 (ksize).
 
 The method is the one of tests/misc_cases.py and tests/blur_cases.py.  The conv contractions are fp32 arithmetic
 (v_mfma_f32_32x32x2_f32 and plain FMAs): on integer operands whose products sum to less than 2^24 every
@@ -9,13 +10,13 @@ float32 number, so a correct kernel equals the float64 oracle bit for bit and a 
 by at least 1.
 
 Two recipes per case:
-  dense     x, w, dy integers in [-m, m], m = min(3, isqrt((2^24 - 1) // K)) with K the contraction length (25 Cin forward,
-            25 Cout data gradient, M = B Ho Wo filter gradient): K m^2 < 2^24.
-  decode    forward / data gradient: the activation is one-hot in the channel at impulses at Chebyshev distance >= 5 from each
-            other (no output window holds two), placed at the four corners, on both sides of the tile / strip seams of the case's
-            route, then a seeded fill, a different set per image; the weights are 1 + tap + 25 (ci + Cin co), all distinct and
-            < 2^24 up to 512 x 512 channels.  Every output is ONE weight or 0, so a wrong output names the (tap, ci, co) that
-            reached it (decode_weight).
+  dense     x, w, dy integers in [-m, m], m = min(3, isqrt((2^24 - 1) // K)) with K the contraction length (k k Cin forward,
+            k k Cout data gradient, M = B Ho Wo filter gradient): K m^2 < 2^24.
+  decode    forward / data gradient: the activation is one-hot in the channel at impulses at Chebyshev distance >= k from each
+            other (no output window holds two; at k = 1 every pixel may hold one), placed at the four corners, on both sides of
+            the tile / strip seams of the case's route, then a seeded fill, a different set per image; the weights are
+            1 + tap + k k (ci + Cin co), all distinct and < 2^24 up to 512 x 512 channels at k = 5.  Every output is ONE weight or
+            0, so a wrong output names the (tap, ci, co) that reached it (decode_weight).
             filter gradient: x dense in [-3, 3]; every dy channel is zero but for at most 7 pixels that hold 8^0 .. 8^6 -- at the
             first and last pixel, on both sides of the split (chunk) seams, of the 32-pixel steps and of the image seams, the
             rest seeded.  dw[tap, ci, co] = sum_j x[pixel_j + tap, ci] 8^j is a balanced base-8 number whose digit j is the x
@@ -52,6 +53,11 @@ OFF = frozenset(k for k in SWITCHED_ENV if k in os.environ)      # getenv(...) ?
 
 def cdiv(a, b):
     return -(-a // b)
+
+
+def ksize(case):
+    """The kernel size of a case shape (B, H, W, Cin, Cout, stride[, k]): the optional seventh element, 5 without it."""
+    return case[6] if len(case) > 6 else K5
 
 
 def same_pads(n, k, s):
@@ -187,6 +193,14 @@ def _ntap_w(p):
     """conv_igemm.hip:1387-1389: weight taps the launch addresses."""
     w = [t[2] + 1 for g in p["ph"] for t in g["taps"]]
     return max(w) if w else 0
+
+
+def tapless_groups(p, pmerge):
+    """Phase groups of a launch (conv_igemm.hip:100-135: group g is phases g and nphase - 1 - g at pmerge 2, else pmerge consecutive
+    phases) none of whose phases has a tap: a 1x1 stride-2 data gradient has three such phases, and the merged pair (1, 2) is one."""
+    nph = len(p["ph"])
+    phases = lambda g: (g, nph - 1 - g) if pmerge == 2 else range(g * pmerge, (g + 1) * pmerge)
+    return [g for g in range(nph // pmerge) if not any(p["ph"][q]["taps"] for q in phases(g))]
 
 
 def try_c16(bwd, B, H, W, Ci, Co, k, s):
@@ -405,7 +419,7 @@ def plan_wgrad(B, H, W, Ci, Co, s, k=K5):
     mfma = Ci % 4 == 0 and Co % 4 == 0 and Ci >= 16 and Co >= 16
     thin_ci = Ci <= 4 and Co % 4 == 0 and Co >= 16 and kk * Ci <= 128
     thin_co = Co <= 4 and Ci % 4 == 0 and Ci >= 16 and s == 1 and kk * Co <= 128
-    pl = dict(mode=None, ksplit=1, chunk=0, tiles_m=1, tiles_n=1, bkp=0, always_slab=0, taps_in_grid=0, M=M, Ho=Ho, Wo=Wo, nout=nout)
+    pl = dict(mode=None, ksplit=1, chunk=0, tiles_m=1, tiles_n=1, bkp=0, always_slab=0, taps_in_grid=0, M=M, Ho=Ho, Wo=Wo, nout=nout, k=k)
 
     def done():
         lg2 = lambda v: max(0, (v - 1).bit_length())
@@ -550,7 +564,7 @@ def dense(B, H, W, Ci, Co, s, op, seed=0, k=K5):
 
 
 def decode_weights(Ci, Co, k=K5):
-    """w[kh, kw, ci, co] = 1 + tap + 25 (ci + Cin co): all distinct, < 2^24 up to 512 x 512 channels."""
+    """w[kh, kw, ci, co] = 1 + tap + k k (ci + Cin co): all distinct, < 2^24 (asserted; up to 512 x 512 channels at k = 5)."""
     tap = np.arange(k * k).reshape(k, k, 1, 1)
     w = 1 + tap + k * k * (np.arange(Ci).reshape(1, 1, Ci, 1) + Ci * np.arange(Co).reshape(1, 1, 1, Co))
     assert w.max() < TWO24
@@ -594,8 +608,10 @@ def impulses(shape, seam_rows=(), seam_cols=(), seed=0, k=K5):
     return a
 
 
-def seams(bwd, B, H, W, Ci, Co, s, d):
-    """Rows and columns of the ACTIVATION (x forward, dy data gradient) that lie beside a tile / strip / phase seam of route d."""
+def seams(bwd, B, H, W, Ci, Co, s, d, k=K5):
+    """Rows and columns of the ACTIVATION (x forward, dy data gradient) that lie beside a tile / strip / phase seam of route d; for
+    k < 5 also the rows and columns on either side of the line where a window stops holding padding taps (the 5x5 tables keep the
+    impulse sets they were proven on)."""
     Ho, Wo = cdiv(H, s), cdiv(W, s)
     Ha, Wa = (Ho, Wo) if bwd else (H, W)                # the activation's map
     to_act = (lambda o: o // s) if bwd else (lambda o: o * s)     # an output row / column -> the activation row / column under it
@@ -620,27 +636,31 @@ def seams(bwd, B, H, W, Ci, Co, s, d):
     elif f in ("conv_thin_n_patch_all", "conv_thin_n_patch", "conv_thin_k_mfma", "conv_thin_n_mfma"):
         rows |= {to_act(r) for r in (3, 4, 7, 8, 15, 16) if r < oH}
         cols |= {to_act(c) for c in (15, 16, 31, 32, 63, 64) if c < oW}
+    if k < K5:
+        lo = k // 2                                          # the widest SAME pad: rows / columns lo - 1 and lo straddle its reach
+        rows |= {r for r in (lo - 1, lo, Ha - 1 - lo, Ha - lo) if r >= 0}
+        cols |= {c for c in (lo - 1, lo, Wa - 1 - lo, Wa - lo) if c >= 0}
     return [r for r in rows if r < Ha], [c for c in cols if c < Wa]
 
 
 def make_fwd(case, recipe, seed=0):
     """-> (x, w) float64 for conv2d_fwd."""
-    B, H, W, Ci, Co, s = case[:6]
+    (B, H, W, Ci, Co, s), k = case[:6], ksize(case)
     if recipe == "dense":
-        x, w, _ = dense(B, H, W, Ci, Co, s, "fwd", seed)
+        x, w, _ = dense(B, H, W, Ci, Co, s, "fwd", seed, k)
         return x, w
-    r, c = seams(0, B, H, W, Ci, Co, s, route(0, B, H, W, Ci, Co, s))
-    return impulses((B, H, W, Ci), r, c, seed), decode_weights(Ci, Co)
+    r, c = seams(0, B, H, W, Ci, Co, s, route(0, B, H, W, Ci, Co, s, k), k)
+    return impulses((B, H, W, Ci), r, c, seed, k), decode_weights(Ci, Co, k)
 
 
 def make_dgrad(case, recipe, seed=0):
     """-> (dy, w) float64 for conv2d_bwd_data."""
-    B, H, W, Ci, Co, s = case[:6]
+    (B, H, W, Ci, Co, s), k = case[:6], ksize(case)
     if recipe == "dense":
-        _, w, dy = dense(B, H, W, Ci, Co, s, "dgrad", seed + 1)
+        _, w, dy = dense(B, H, W, Ci, Co, s, "dgrad", seed + 1, k)
         return dy, w
-    r, c = seams(1, B, H, W, Ci, Co, s, route(1, B, H, W, Ci, Co, s))
-    return impulses((B, cdiv(H, s), cdiv(W, s), Co), r, c, seed + 1), decode_weights(Ci, Co)
+    r, c = seams(1, B, H, W, Ci, Co, s, route(1, B, H, W, Ci, Co, s, k), k)
+    return impulses((B, cdiv(H, s), cdiv(W, s), Co), r, c, seed + 1, k), decode_weights(Ci, Co, k)
 
 
 WG_DIGITS = 7          # 8^0 .. 8^6 per dy channel: 3 (8^7 - 1) / 7 = 898 779 < 2^24
@@ -667,11 +687,11 @@ def wgrad_seam_pixels(pl, B):
 
 def make_wgrad(case, recipe, seed=0):
     """-> (x, dy) float64 for conv2d_bwd_filter, plus the pixel table [Co, 7] of the decode recipe (None for dense)."""
-    B, H, W, Ci, Co, s = case[:6]
-    x, _, dy = dense(B, H, W, Ci, Co, s, "wgrad", seed + 2)
+    (B, H, W, Ci, Co, s), k = case[:6], ksize(case)
+    x, _, dy = dense(B, H, W, Ci, Co, s, "wgrad", seed + 2, k)
     if recipe == "dense":
         return x, dy, None
-    pl = plan_wgrad(B, H, W, Ci, Co, s)
+    pl = plan_wgrad(B, H, W, Ci, Co, s, k)
     M = pl["M"]
     rng = np.random.default_rng([seed, 77, B, H, W, Ci, Co, s])
     x = rng.integers(-3, 4, size=x.shape).astype(np.float64)
@@ -719,13 +739,13 @@ def decode_wgrad(got, ref, pix, case):
             f"expected {ref[kh, kw, ci, co]!r}; {where}")
 
 
-def describe_wrong(y, ref, Ci, recipe, bwd):
+def describe_wrong(y, ref, Ci, recipe, bwd, k=K5):
     """Text for a wrong forward / data-gradient output: how many, never-written count, and for the decode recipe the weights."""
     bad = np.argwhere(y != ref)
     i = tuple(int(v) for v in bad[0])
     txt = f"{len(bad)} of {ref.size} wrong, {int(np.isnan(y).sum())} never written; first at (b, h, w, c)={i}: got {y[i]!r}, expected {ref[i]!r}"
     if recipe == "decode":
-        txt += f"; got weight (kh, kw, ci, co)={decode_weight(y[i], Ci)}, expected {decode_weight(ref[i], Ci)}"
+        txt += f"; got weight (kh, kw, ci, co)={decode_weight(y[i], Ci, k)}, expected {decode_weight(ref[i], Ci, k)}"
     return txt
 
 
@@ -740,8 +760,8 @@ def ref_dgrad(dy, w, s, hw):
     return O.conv2d_bwd_data(dy, w, s, hw)
 
 
-def ref_wgrad(x, dy, s):
-    return O.conv2d_bwd_filter(x, dy, s, K5)
+def ref_wgrad(x, dy, s, k=K5):
+    return O.conv2d_bwd_filter(x, dy, s, k)
 
 
 def epilogue_ref(z, mode, bias=None, mul=None, ref_act=None, keep=None, keep_elems=0, alpha=0.25, scale=2.0):
@@ -902,4 +922,5 @@ def run_switched_child(mode):
 
 
 def case_id(shape):
-    return "x".join(map(str, shape[:5])) + f"s{shape[5]}"
+    """B x H x W x Cin x Cout s stride, and k<size> for a shape that carries one."""
+    return "x".join(map(str, shape[:5])) + f"s{shape[5]}" + (f"k{shape[6]}" if len(shape) > 6 else "")

@@ -12,6 +12,9 @@ case names the (tap, ci, co) or the dy pixel its first wrong output came from.
 The fallbacks behind the once-read switches that take a 5x5-only fast path away (conv_cases.SWITCHED_ENV) run in ONE fresh child
 process started with them set (tests/conv_switched_child.py); no process that has initialised the GPU replaces its program.
 
+The runner and the check_* bodies take the kernel size from the case shape (its optional seventh element, 5 without one):
+tests/test_conv_ksize_exact_gpu.py imports them and runs the tables of tests/conv_ksize_cases.py at k = 3 and 1 through them.
+
 Not here: tanh (inexact; tests/test_conv_gpu.py holds it to a tolerance) and the tuning
 aids among the once-read switches (the rest of conv_cases.STATIC_SWITCHES).  The split-bf16 kernel (conv_math="bf16x6") has its own
 exact file, tests/test_conv_x6_exact_gpu.py, which borrows the guarded buffers of this one."""
@@ -86,15 +89,15 @@ def run_route(bwd, shape, act, w, epi_kw=None, out_init=None, stats=None, profil
     """bg_conv2d_fwd / bg_conv2d_bwd_data on guarded buffers -> (output as float64, route description); checks the workspace query,
     the launch names, the gather-GEMM's tile and slab count, the guard bands and the inputs."""
     from blurred_gan_amd import ops
-    B, H, W, Ci, Co, s = shape
+    (B, H, W, Ci, Co, s), k = shape[:6], CC.ksize(shape)
     Ho, Wo = CC.cdiv(H, s), CC.cdiv(W, s)
     out_shape = (B, H, W, Ci) if bwd else (B, Ho, Wo, Co)
-    d = CC.route(bwd, *shape, stats=stats is not None, workspace=workspace)
+    d = CC.route(bwd, B, H, W, Ci, Co, s, k, stats=stats is not None, workspace=workspace)
     ga = Guarded(act.size, act)
     gw = Guarded(w.size, w if bwd else np.transpose(w, (0, 1, 3, 2)))
     go = Guarded(int(np.prod(out_shape)), out_init)
-    nb = ops.conv2d_splitk_workspace_bytes(bwd, B, H, W, Ci, Co, 5, s)
-    assert nb == CC.splitk_workspace_bytes(bwd, B, H, W, Ci, Co, 5, s)
+    nb = ops.conv2d_splitk_workspace_bytes(bwd, B, H, W, Ci, Co, k, s)
+    assert nb == CC.splitk_workspace_bytes(bwd, B, H, W, Ci, Co, k, s)
     gs = Guarded(nb // 4) if nb and workspace else None
     kw = dict(epi_kw or {})
     held = {k: v for k, v in kw.items() if isinstance(v, Guarded)}
@@ -103,8 +106,8 @@ def run_route(bwd, shape, act, w, epi_kw=None, out_init=None, stats=None, profil
         kw["ref"] = go.view
     epi = ops.epilogue(ws=gs.view if gs else None, stats=stats.view if stats else None, **kw) if (kw or gs or stats) else None
     a4 = ga.t(B, Ho, Wo, Co) if bwd else ga.t(B, H, W, Ci)
-    fn = (lambda: ops.conv2d_bwd_data(a4, gw.view, go.t(*out_shape), 5, s, epi)) if bwd else \
-         (lambda: ops.conv2d_fwd(a4, gw.view, go.t(*out_shape), 5, s, epi))
+    fn = (lambda: ops.conv2d_bwd_data(a4, gw.view, go.t(*out_shape), k, s, epi)) if bwd else \
+         (lambda: ops.conv2d_fwd(a4, gw.view, go.t(*out_shape), k, s, epi))
     if profile:
         rec = launches(fn)
         assert [r[0] for r in rec] == d["names"], ([r[0] for r in rec], d)
@@ -119,37 +122,41 @@ def run_route(bwd, shape, act, w, epi_kw=None, out_init=None, stats=None, profil
     return go.get(out_shape), d
 
 
+def make_route(bwd, shape, recipe, seed=0):
+    """-> (activation, w, float64 reference) of the forward (x) or the data gradient (dy) of a case shape."""
+    act, w = (CC.make_dgrad if bwd else CC.make_fwd)(shape, recipe, seed)
+    return act, w, (CC.ref_dgrad(act, w, shape[5], shape[1:3]) if bwd else CC.ref_fwd(act, w, shape[5]))
+
+
+def check_route_exact(bwd, shape):
+    """Both recipes of one direction of a case (k is the shape's seventh element, 5 without one), on its restated route."""
+    for recipe in ("dense", "decode"):
+        act, w, ref = make_route(bwd, shape, recipe)
+        out, _ = run_route(bwd, shape, act, w)
+        if not np.array_equal(out, ref):
+            pytest.fail(f"{'data gradient' if bwd else 'forward'} {CC.case_id(shape)} [{recipe}]: "
+                        f"{CC.describe_wrong(out, ref, shape[3], recipe, bwd, CC.ksize(shape))}")
+
+
 @pytest.mark.parametrize("case", CC.ROUTE_CASES, ids=ROUTE_IDS)
 def test_forward_exact_on_its_route(case):
-    shape = case[0]
-    for recipe in ("dense", "decode"):
-        x, w = CC.make_fwd(shape, recipe)
-        ref = CC.ref_fwd(x, w, shape[5])
-        y, _ = run_route(0, shape, x, w)
-        if not np.array_equal(y, ref):
-            pytest.fail(f"forward {CC.case_id(shape)} [{recipe}]: {CC.describe_wrong(y, ref, shape[3], recipe, 0)}")
+    check_route_exact(0, case[0])
 
 
 @pytest.mark.parametrize("case", CC.ROUTE_CASES, ids=ROUTE_IDS)
 def test_data_gradient_exact_on_its_route(case):
-    shape = case[0]
-    for recipe in ("dense", "decode"):
-        dy, w = CC.make_dgrad(shape, recipe)
-        ref = CC.ref_dgrad(dy, w, shape[5], shape[1:3])
-        dx, _ = run_route(1, shape, dy, w)
-        if not np.array_equal(dx, ref):
-            pytest.fail(f"data gradient {CC.case_id(shape)} [{recipe}]: {CC.describe_wrong(dx, ref, shape[3], recipe, 1)}")
+    check_route_exact(1, case[0])
 
 
 def run_wgrad(shape, x, dy, dw0=None, beta=0.0, scale=1.0, profile=True):
     from blurred_gan_amd import ops
-    B, H, W, Ci, Co, s = shape
-    pl = CC.plan_wgrad(*shape)
-    nb = ops.conv2d_bwd_filter_workspace_bytes(B, H, W, Ci, Co, 5, s)
+    (B, H, W, Ci, Co, s), k = shape[:6], CC.ksize(shape)
+    pl = CC.plan_wgrad(B, H, W, Ci, Co, s, k)
+    nb = ops.conv2d_bwd_filter_workspace_bytes(B, H, W, Ci, Co, k, s)
     assert nb == pl["ws_bytes"], (nb, pl)                                       # the slab count pins the modes that share a name
-    gx, gy, gd = Guarded(x.size, x), Guarded(dy.size, dy), Guarded(25 * Ci * Co, dw0)
+    gx, gy, gd = Guarded(x.size, x), Guarded(dy.size, dy), Guarded(k * k * Ci * Co, dw0)
     gs = Guarded(nb // 4) if nb else None
-    fn = lambda: ops.conv2d_bwd_filter(gx.t(*x.shape), gy.t(*dy.shape), gd.t(5, 5, Ci, Co), 5, s, beta, scale, gs.view if gs else None)
+    fn = lambda: ops.conv2d_bwd_filter(gx.t(*x.shape), gy.t(*dy.shape), gd.t(k, k, Ci, Co), k, s, beta, scale, gs.view if gs else None)
     if profile:
         names = [r[0] for r in launches(fn)]
         assert names == pl["names"], (names, pl)
@@ -157,18 +164,16 @@ def run_wgrad(shape, x, dy, dw0=None, beta=0.0, scale=1.0, profile=True):
         fn()
         torch.cuda.synchronize()
     check_buffers([gx, gy], [gd, gs])
-    return gd.get((5, 5, Ci, Co))
+    return gd.get((k, k, Ci, Co))
 
 
-@pytest.mark.parametrize("case", CC.WGRAD_CASES, ids=WGRAD_IDS)
-def test_filter_gradient_exact_on_its_mode(case):
+def check_filter_gradient_exact(shape):
     """beta = 0 into a NaN dw, then the accumulate form 0.5 dw0 + 2 grad on a dw of even integers (powers of two: exact)."""
-    shape = case[0]
-    Ci, Co = shape[3], shape[4]
-    dw0 = 2.0 * np.random.default_rng(5).integers(-4, 5, size=(5, 5, Ci, Co))
+    Ci, Co, k = shape[3], shape[4], CC.ksize(shape)
+    dw0 = 2.0 * np.random.default_rng(5).integers(-4, 5, size=(k, k, Ci, Co))
     for recipe in ("dense", "decode"):
         x, dy, pix = CC.make_wgrad(shape, recipe)
-        ref = CC.ref_wgrad(x, dy, shape[5])
+        ref = CC.ref_wgrad(x, dy, shape[5], k)
         for form, (init, beta, scale, want) in {"beta=0": (None, 0.0, 1.0, ref), "accumulate": (dw0, 0.5, 2.0, 0.5 * dw0 + 2.0 * ref)}.items():
             dw = run_wgrad(shape, x, dy, init, beta, scale)
             if not np.array_equal(dw, want):
@@ -178,15 +183,18 @@ def test_filter_gradient_exact_on_its_mode(case):
                 pytest.fail(f"filter gradient {CC.case_id(shape)} [{recipe}, {form}]: {int(np.isnan(dw).sum())} never written; {detail}")
 
 
+@pytest.mark.parametrize("case", CC.WGRAD_CASES, ids=WGRAD_IDS)
+def test_filter_gradient_exact_on_its_mode(case):
+    check_filter_gradient_exact(case[0])
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # epilogues: everything but tanh is exact on this data (integer bias and multipliers, alpha = 1/4, dropout scale 2)
 # ------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bwd,shape", CC.EPI_CASES, ids=[way_id(t) for t in CC.EPI_CASES])
-def test_epilogues_exact(bwd, shape):
+def check_epilogues_exact(bwd, shape):
     from blurred_gan_amd._lib import EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_NONE, EPI_AFFINE_LRELU
-    B, H, W, Ci, Co, s = shape
-    act, w = (CC.make_dgrad if bwd else CC.make_fwd)(shape, "dense", seed=3)
-    z = CC.ref_dgrad(act, w, s, (H, W)) if bwd else CC.ref_fwd(act, w, s)
+    B, Ci, k = shape[0], shape[3], CC.ksize(shape)
+    act, w, z = make_route(bwd, shape, "dense", seed=3)
     N = z.shape[-1]
     rng = np.random.default_rng([9, bwd, *shape])
     bias, mul = rng.integers(-5, 6, N).astype(np.float64), rng.integers(-3, 4, N).astype(np.float64)
@@ -211,18 +219,23 @@ def test_epilogues_exact(bwd, shape):
     }
     for name, (kw, out_init, want) in variants.items():
         got, d = run_route(bwd, shape, act, w, epi_kw=kw, out_init=out_init)
-        assert np.array_equal(got, want), f"{d['names'][0]} {CC.case_id(shape)} [{name}]: {CC.describe_wrong(got, want, Ci, 'dense', bwd)}"
+        assert np.array_equal(got, want), f"{d['names'][0]} {CC.case_id(shape)} [{name}]: {CC.describe_wrong(got, want, Ci, 'dense', bwd, k)}"
 
 
-@pytest.mark.parametrize("bwd,shape", CC.STATS_CASES, ids=[way_id(t) for t in CC.STATS_CASES])
-def test_statistics_epilogue_exact(bwd, shape):
+@pytest.mark.parametrize("bwd,shape", CC.EPI_CASES, ids=[way_id(t) for t in CC.EPI_CASES])
+def test_epilogues_exact(bwd, shape):
+    check_epilogues_exact(bwd, shape)
+
+
+def check_statistics_epilogue_exact(bwd, shape):
     """bg_epilogue.stats: the partial rows sum EXACTLY to the column sums and sums of squares of the stored tensor (impulse
     activations and weights in [-3, 3]: every output is one weight, so a partial row's sum of squares is far below 2^24); the rows
-    past the reported count are never written."""
+    past the reported count are never written, and the rows of a workgroup whose phases have no tap at all (one row per phase group
+    and M tile, conv_igemm.hip:143) are exact zeros."""
     from blurred_gan_amd import ops
-    B, H, W, Ci, Co, s = shape
+    (B, H, W, Ci, Co, s), k = shape[:6], CC.ksize(shape)
     act, _ = (CC.make_dgrad if bwd else CC.make_fwd)(shape, "decode", seed=4)
-    _, w, _ = CC.dense(B, H, W, Ci, Co, s, "fwd", seed=4)
+    _, w, _ = CC.dense(B, H, W, Ci, Co, s, "fwd", 4, k)
     ref = CC.ref_dgrad(act, w, s, (H, W)) if bwd else CC.ref_fwd(act, w, s)
     N = ref.shape[-1]
     assert np.abs(ref).max() <= 3 and ref.any()
@@ -230,24 +243,29 @@ def test_statistics_epilogue_exact(bwd, shape):
     out, d = run_route(bwd, shape, act, w, stats=gst, workspace=False)
     rows = ops.conv2d_stats_rows(d["epi"])
     assert rows == d["stats_rows"] > 0, (rows, d)
-    assert np.array_equal(out, ref), CC.describe_wrong(out, ref, Ci, "dense", bwd)
+    assert np.array_equal(out, ref), CC.describe_wrong(out, ref, Ci, "dense", bwd, k)
     st = gst.get(-1)
     part = st[:rows * 2 * N].reshape(rows, 2, N)
     assert np.isfinite(part).all(), f"{int((~np.isfinite(part)).sum())} partial sums never written"
     assert np.isnan(st[rows * 2 * N:]).all(), "rows past the reported count were written"
     flat = ref.reshape(-1, N)
     assert np.array_equal(part[:, 0].sum(0), flat.sum(0)) and np.array_equal(part[:, 1].sum(0), (flat ** 2).sum(0))
+    for grp in CC.tapless_groups(CC.gather_params(bwd, B, H, W, Ci, Co, k, s), d["pmerge"]):
+        assert not part[grp * d["mtiles"]:(grp + 1) * d["mtiles"]].any(), f"phase group {grp} has no tap: its rows are not exact zeros"
+
+
+@pytest.mark.parametrize("bwd,shape", CC.STATS_CASES, ids=[way_id(t) for t in CC.STATS_CASES])
+def test_statistics_epilogue_exact(bwd, shape):
+    check_statistics_epilogue_exact(bwd, shape)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # isolation
 # ------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bwd,shape", CC.ISOLATION_ROUTES, ids=[way_id(t) for t in CC.ISOLATION_ROUTES])
-def test_a_nan_image_stays_inside_itself(bwd, shape):
+def check_a_nan_image_stays_inside_itself(bwd, shape):
     """One image of the batch is NaN throughout: every other image equals its reference."""
-    B, H, W, Ci, Co, s = shape
-    act, w = (CC.make_dgrad if bwd else CC.make_fwd)(shape, "dense", seed=6)
-    ref = CC.ref_dgrad(act, w, s, (H, W)) if bwd else CC.ref_fwd(act, w, s)
+    B = shape[0]
+    act, w, ref = make_route(bwd, shape, "dense", seed=6)
     k = B // 2
     act[k] = np.nan
     out, _ = run_route(bwd, shape, act, w, profile=False)
@@ -258,22 +276,34 @@ def test_a_nan_image_stays_inside_itself(bwd, shape):
 
 
 @pytest.mark.parametrize("bwd,shape", CC.ISOLATION_ROUTES, ids=[way_id(t) for t in CC.ISOLATION_ROUTES])
-def test_two_runs_are_bit_identical(bwd, shape):
+def test_a_nan_image_stays_inside_itself(bwd, shape):
+    check_a_nan_image_stays_inside_itself(bwd, shape)
+
+
+def check_two_runs_are_bit_identical(bwd, shape):
     """No route of the forward / data gradient has atomics: two runs into different buffers agree bit for bit (and are right)."""
-    B, H, W, Ci, Co, s = shape
-    act, w = (CC.make_dgrad if bwd else CC.make_fwd)(shape, "dense", seed=7)
+    act, w, ref = make_route(bwd, shape, "dense", seed=7)
     a, _ = run_route(bwd, shape, act, w, profile=False)
     b, _ = run_route(bwd, shape, act, w, profile=False)
-    assert np.array_equal(a, b) and np.array_equal(a, CC.ref_dgrad(act, w, s, (H, W)) if bwd else CC.ref_fwd(act, w, s))
+    assert np.array_equal(a, b) and np.array_equal(a, ref)
 
 
-@pytest.mark.parametrize("shape", CC.ISOLATION_WGRAD, ids=[CC.case_id(c) for c in CC.ISOLATION_WGRAD])
-def test_two_filter_gradient_runs_are_bit_identical(shape):
+@pytest.mark.parametrize("bwd,shape", CC.ISOLATION_ROUTES, ids=[way_id(t) for t in CC.ISOLATION_ROUTES])
+def test_two_runs_are_bit_identical(bwd, shape):
+    check_two_runs_are_bit_identical(bwd, shape)
+
+
+def check_two_filter_gradient_runs_are_bit_identical(shape):
     """The filter gradients reduce through slabs, not atomics: two runs into different buffers agree bit for bit."""
     x, dy, _ = CC.make_wgrad(shape, "dense", seed=8)
     a = run_wgrad(shape, x, dy, profile=False)
     b = run_wgrad(shape, x, dy, profile=False)
-    assert np.array_equal(a, b) and np.array_equal(a, CC.ref_wgrad(x, dy, shape[5]))
+    assert np.array_equal(a, b) and np.array_equal(a, CC.ref_wgrad(x, dy, shape[5], CC.ksize(shape)))
+
+
+@pytest.mark.parametrize("shape", CC.ISOLATION_WGRAD, ids=[CC.case_id(c) for c in CC.ISOLATION_WGRAD])
+def test_two_filter_gradient_runs_are_bit_identical(shape):
+    check_two_filter_gradient_runs_are_bit_identical(shape)
 
 
 def test_fallbacks_behind_the_once_read_switches_in_a_fresh_process():
