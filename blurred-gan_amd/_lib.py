@@ -73,7 +73,13 @@ SIGNATURES = {
     "bg_bn_bwd_stats_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _p, _z, _p]),
     "bg_bn_bwd_apply_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p]),
     "bg_bn_param_grads_f32": (_i, [_p, _i, _f, _p, _p, _p]),
-    "bg_lerp_f32": (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    "bg_ln_route": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "bg_ln_workspace_bytes": (_z, [_i, _i]),
+    "bg_ln_fwd_f32": (_i, [_p, _p, _i, _i, _p, _p, _f, _f, _p, _f, _z, _p, _p, _p]),
+    "bg_ln_bwd_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _f, _z, _p, _p, _i, _i, _p, _p, _i, _f, _f, _p, _z, _p]),
+    "bg_ln_tangent_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p]),
+    "bg_ln_gp_source_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _f, _p, _z, _p]),
+    "bg_lerp_f32":(_i, [_p, _p, _p, _p, _i, _i, _p]),
     "bg_row_norm_f32": (_i, [_p, _p, _i, _i, _p]),
     "bg_gp_seed_f32": (_i, [_p, _p, _f, _p, _i, _i, _p]),
     "bg_gp_seed_guarded_f32": (_i, [_p, _p, _f, _p, _i, _i, _p]),

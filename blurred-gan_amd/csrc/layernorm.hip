@@ -1,0 +1,604 @@
+// Layer normalisation over the channel axis of NHWC fp32 maps (include/bgan.h "layer normalisation"): the kernels behind
+// layers.LayerNormalization in the critic -- forward (+ LeakyReLU + Dropout), backward, the gradient penalty's tangent and its
+// second-order source.  Data is [R, C]: R = B*H*W rows of C contiguous channels; every statistic is a mean over ONE row, so rows
+// are independent and the kernels are pure streaming.
+//
+// Per row, with all means over the row's C channels: mu, r = 1/sqrt(var + eps) (biased variance; saved by the forward),
+// xh = (z - mu) * r, and the Jacobian of z -> xh is the symmetric operator  M y = r * (yc - xh * mean(yc * xh)),  yc = y - mean(y).
+//
+// Routes (bg_ln_route reports the one a C takes).  A row is read in units of one float4 (C % 4 == 0) or one float (any other C):
+// U = C / 4 or C units.  L = the power of two >= U, at most 64, lanes share a row, so a wave holds 64 / L rows; with U > 64 each
+// lane keeps 2 or 4 units (U <= 128, U <= 256).  Up to there a row is read ONCE and stays in registers between its statistics and
+// its use.  Beyond (C > 1024, or C > 256 and not a multiple of 4) the row is cut into chunks of 64 units, one per lane, along
+// gridDim.y: a workgroup sweeps the whole row from memory for the statistics (the re-read hits L2) and keeps only its own chunk in
+// registers.  (One unit per lane there: with more, the sweeps' address and mask bookkeeping no longer fits the scalar registers.)
+// A workgroup is 4 waves = 4 * 64 / L rows per visit, in a grid-stride loop over at most 1024 workgroups.
+//
+// Column sums (dgamma, dbeta) are deterministic: each lane adds its own channels over the rows it visits, in visit order; the
+// lanes of a wave that share a channel are folded by a fixed shuffle tree, the four waves through LDS in wave order, and one
+// partial row per workgroup goes to the workspace; ln_finish_kernel adds the partial rows in a fixed order (64 strided lanes and
+// a shuffle tree per channel).  No atomics: two runs give the same bits.  LDS holds that cross-wave scratch and nothing else.
+#include "common.h"
+#include <algorithm>
+
+namespace {
+
+constexpr int kT = 256, kWaves = kT / 64, kMaxBlocks = 1024, kChunkUnits = 64;
+
+struct Route { int vec, lg, nv, chunks; };
+
+inline Route route_for(int C) {
+  Route t;
+  t.vec = C % 4 == 0 ? 4 : 1;
+  const int U = C / t.vec;
+  t.lg = 0;
+  while ((1 << t.lg) < U && t.lg < 6) ++t.lg;
+  const int per = (U + 63) / 64;
+  t.nv = per <= 1 ? 1 : per <= 2 ? 2 : 4;
+  t.chunks = per <= 4 ? 1 : (U + kChunkUnits - 1) / kChunkUnits;
+  if (t.chunks > 1) t.nv = 1;
+  return t;
+}
+
+struct Geo { int R, C, U, lg; };
+
+// the units one lane holds of one row: unit base + j * L + sub for j < NV (zeros where unit_ok says there is none)
+template <int VEC, int NV>
+struct Tile {
+  float v[NV][VEC];
+};
+
+template <int VEC>
+__device__ __forceinline__ void load_unit(const float* p, size_t unit, float (&d)[VEC]) {
+  if constexpr (VEC == 4) {
+    const float4 t = reinterpret_cast<const float4*>(p)[unit];
+    d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
+  } else {
+    d[0] = p[unit];
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_unit(float* p, size_t unit, const float (&d)[VEC]) {
+  if constexpr (VEC == 4) reinterpret_cast<float4*>(p)[unit] = make_float4(d[0], d[1], d[2], d[3]);
+  else p[unit] = d[0];
+}
+
+// keep bytes of one unit, one per element (nonzero = kept)
+template <int VEC>
+__device__ __forceinline__ void load_keep(const uint8_t* __restrict__ k, size_t unit, unsigned (&d)[VEC]) {
+  if constexpr (VEC == 4) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(k)[unit];
+    d[0] = w & 0xffu; d[1] = (w >> 8) & 0xffu; d[2] = (w >> 16) & 0xffu; d[3] = w >> 24;
+  } else {
+    d[0] = k[unit];
+  }
+}
+
+// where one lane stands in one visit of its workgroup
+struct Pos {
+  int L, sub, U;
+  size_t row, unit0;      // unit0: index of the row's first unit in the matrix
+  bool row_ok;
+};
+
+// whether unit j of the tile at ``base`` exists: inside the row, in a row of the matrix.  Recomputed wherever it is needed (a
+// compare) rather than kept: a kept flag per unit is a lane mask in a scalar register pair
+__device__ __forceinline__ bool unit_ok(const Pos& q, int base, int j) { return q.row_ok && base + j * q.L + q.sub < q.U; }
+
+template <int VEC, int NV>
+__device__ __forceinline__ Tile<VEC, NV> load_tile(const float* __restrict__ p, const Pos& q, int base) {
+  Tile<VEC, NV> t;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) t.v[j][e] = 0.f;
+    if (unit_ok(q, base, j)) load_unit<VEC>(p, q.unit0 + base + j * q.L + q.sub, t.v[j]);
+  }
+  return t;
+}
+
+// sum over the lanes that share a row (L a power of two, groups aligned to L: the butterfly never leaves the group)
+__device__ __forceinline__ float group_sum(float v, int L) {
+  for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// body(tile, its base) over what feeds a row's statistics: the lane's own registers, or on the chunked route every chunk of the row
+// from memory
+template <bool LOOP, int NV, class T, class Load, class Body>
+__device__ __forceinline__ void sweep(int U, const T& own, int base, Load load, Body body) {
+  if constexpr (!LOOP) {
+    body(own, base);
+  } else {
+    for (int b = 0; b < U; b += 64 * NV) body(load(b), b);
+  }
+}
+
+// the forward's pre-activation, operation for operation: every kernel that needs LeakyReLU's branch re-derives it from z with this
+// expression on the same inputs, so the branch is the forward's bit for bit (alpha >= 0) and the activation itself is never re-read
+__device__ __forceinline__ float ln_pre(float z, float mu, float r, float g, float b) { return g * ((z - mu) * r) + b; }
+
+// per-lane column accumulators -> one partial row of this workgroup: partial[(blockIdx.x * NQ + q) * C + c]
+template <int VEC, int NV, int NQ>
+__device__ __forceinline__ void write_partials(float (&acc)[NQ][NV][VEC], const Geo& g, int base, float* __restrict__ partial) {
+  __shared__ float red[kWaves][NQ * NV * VEC][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, L = 1 << g.lg;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float v = acc[q][j][e];
+        for (int o = 32; o >= L; o >>= 1) v += __shfl_xor(v, o, 64);      // the rows of this wave
+        red[wave][(q * NV + j) * VEC + e][lane] = v;
+      }
+  __syncthreads();
+  if (wave == 0 && lane < L) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const int u = base + j * L + lane;
+        if (u < g.U) {
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            const int k = (q * NV + j) * VEC + e;
+            float s = red[0][k][lane];
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) s += red[w][k][lane];
+            partial[((size_t)blockIdx.x * NQ + q) * g.C + (size_t)u * VEC + e] = s;
+          }
+        }
+      }
+  }
+}
+
+// (means are taken by true division by Cf: a row of equal values then has mean == the value and xh == 0 exactly)
+#define LN_POS_SETUP()                                                                                   \
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rpw = 64 >> g.lg;                          \
+  const int base = LOOP ? (int)blockIdx.y * 64 * NV : 0;                                                 \
+  const size_t groups = ((size_t)g.R + (size_t)rpw * kWaves - 1) / ((size_t)rpw * kWaves);               \
+  const float Cf = (float)g.C;                                                                           \
+  Pos q;                                                                                                \
+  q.L = LOOP ? 64 : 1 << g.lg; /* the chunked route always spreads a row over the whole wave: a constant stride */                                                                                      \
+  q.sub = lane & (q.L - 1);                                                                              \
+  q.U = g.U
+
+#define LN_ROW_SETUP()                                                      \
+  q.row = (rg * kWaves + wave) * (size_t)rpw + (size_t)(lane >> g.lg);      \
+  q.row_ok = q.row < (size_t)g.R;                                           \
+  q.unit0 = q.row * (size_t)g.U
+
+// a = Dropout(LeakyReLU(gamma * xh + beta)); saves mu, r
+template <int MODE, int VEC, int NV, bool LOOP>
+__global__ __launch_bounds__(kT) void ln_fwd_kernel(const float* __restrict__ z, float* __restrict__ a, Geo g,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                    float alpha, const uint8_t* __restrict__ keep, float kscale, size_t keep_rows,
+                                                    float* __restrict__ mu, float* __restrict__ rs) {
+  LN_POS_SETUP();
+  for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
+    LN_ROW_SETUP();
+    auto load = [&](int b) { return load_tile<VEC, NV>(z, q, b); };
+    const Tile<VEC, NV> t = load(base);
+    float s = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Tile<VEC, NV>& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s += x.v[j][e];
+    });
+    const float mean = group_sum(s, q.L) / Cf;
+    float v = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Tile<VEC, NV>& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          const float d = x.v[j][e] - mean;
+          if (unit_ok(q, b, j)) v = fmaf(d, d, v);
+        }
+    });
+    const float r = 1.f / sqrtf(group_sum(v, q.L) / Cf + eps);
+    if (q.row_ok && q.sub == 0 && base == 0) {
+      mu[q.row] = mean;
+      rs[q.row] = r;
+    }
+    const bool masked = keep != nullptr && q.row < keep_rows;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!unit_ok(q, base, j)) continue;
+      const int u = base + j * q.L + q.sub;
+      float gm[VEC], bt[VEC], o[VEC];
+      unsigned kb[VEC];
+      load_unit<VEC>(gamma, (size_t)u, gm);
+      load_unit<VEC>(beta, (size_t)u, bt);
+      if (masked) load_keep<VEC>(keep, q.unit0 + u, kb);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float n = ln_pre(t.v[j][e], mean, r, gm[e], bt[e]);
+        float y = n > 0.f ? n : alpha * n;
+        if (masked) y = kb[e] ? y * kscale : 0.f;
+        o[e] = y;
+      }
+      store_unit<VEC>(a, q.unit0 + u, o);
+    }
+  }
+}
+
+struct ApplyArgs {
+  const float* src;        // MODE 0: the gradient at a; MODE 1: the tangent zdot
+  const float* z;
+  float* out;              // MODE 0: dz; MODE 1: vout
+  const float *gamma, *beta, *mu, *rs;
+  float alpha;
+  const uint8_t* keep;     // MODE 0 only
+  float kscale;
+  size_t keep_rows;
+  const float* addend;     // MODE 0: added to dz (may be NULL)
+  float* u_out;            // MODE 0: u of rows [u_row0, u_row0 + u_rows) (may be NULL)
+  size_t u_row0, u_rows;
+  float* partial;          // MODE 0: column-sum partials of rows [0, dw_rows) (may be NULL)
+  size_t dw_rows;
+};
+
+// MODE 0, backward:  u = g * LeakyReLU' * Dropout',  dz = M(gamma * u) [+ addend],  partials of sum u * xh and sum u
+// MODE 1, tangent:   vout = LeakyReLU' * gamma * M(zdot)
+template <int MODE, int VEC, int NV, bool LOOP>
+__global__ __launch_bounds__(kT) void ln_apply_kernel(ApplyArgs A, Geo g) {
+  LN_POS_SETUP();
+  struct Pair { Tile<VEC, NV> z, u, y; };
+  float acc[2][NV][VEC];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) acc[k][j][e] = 0.f;
+  for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
+    LN_ROW_SETUP();
+    const float mean = q.row_ok ? A.mu[q.row] : 0.f, r = q.row_ok ? A.rs[q.row] : 0.f;
+    const bool masked = MODE == 0 && A.keep != nullptr && q.row < A.keep_rows;
+    // y: the vector M is applied to.  The factor f = LeakyReLU' [* Dropout'] of an element is formed wherever it is needed
+    auto factor = [&](float zv, float gm, float bt, unsigned kb) {
+      float f = ln_pre(zv, mean, r, gm, bt) > 0.f ? 1.f : A.alpha;
+      if (masked) f = kb ? f * A.kscale : 0.f;
+      return f;
+    };
+    auto load = [&](int b) {
+      Pair p;
+      p.z = load_tile<VEC, NV>(A.z, q, b);
+      p.y = load_tile<VEC, NV>(A.src, q, b);
+      p.u = p.y;
+      if constexpr (MODE == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          if (!unit_ok(q, b, j)) continue;
+          const int u = b + j * q.L + q.sub;
+          float gm[VEC], bt[VEC];
+          unsigned kb[VEC];
+          load_unit<VEC>(A.gamma, (size_t)u, gm);
+          load_unit<VEC>(A.beta, (size_t)u, bt);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) kb[e] = 0u;
+          if (masked) load_keep<VEC>(A.keep, q.unit0 + u, kb);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            p.u.v[j][e] = p.y.v[j][e] * factor(p.z.v[j][e], gm[e], bt[e], kb[e]);
+            p.y.v[j][e] = gm[e] * p.u.v[j][e];
+          }
+        }
+      }
+      return p;
+    };
+    const Pair t = load(base);
+    float s = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Pair& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s += x.y.v[j][e];
+    });
+    const float ybar = group_sum(s, q.L) / Cf;
+    float c = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Pair& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          if (unit_ok(q, b, j)) c = fmaf(x.y.v[j][e] - ybar, (x.z.v[j][e] - mean) * r, c);
+    });
+    const float m2 = group_sum(c, q.L) / Cf;
+    const bool keep_u = MODE == 0 && A.u_out != nullptr && q.row >= A.u_row0 && q.row < A.u_row0 + A.u_rows;
+    const bool sums = MODE == 0 && A.partial != nullptr && q.row < A.dw_rows;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!unit_ok(q, base, j)) continue;
+      const int u = base + j * q.L + q.sub;
+      float o[VEC], ad[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) ad[e] = 0.f;
+      if (MODE == 0 && A.addend != nullptr) load_unit<VEC>(A.addend, q.unit0 + u, ad);
+      float gm[VEC], bt[VEC];
+      if constexpr (MODE == 1) {
+        load_unit<VEC>(A.gamma, (size_t)u, gm);
+        load_unit<VEC>(A.beta, (size_t)u, bt);
+      }
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float xh = (t.z.v[j][e] - mean) * r;
+        const float my = r * ((t.y.v[j][e] - ybar) - xh * m2);
+        if constexpr (MODE == 0) {
+          o[e] = A.addend != nullptr ? my + ad[e] : my;
+          if (sums) {
+            acc[0][j][e] = fmaf(t.u.v[j][e], xh, acc[0][j][e]);
+            acc[1][j][e] += t.u.v[j][e];
+          }
+        } else {
+          o[e] = (factor(t.z.v[j][e], gm[e], bt[e], 0u) * gm[e]) * my;
+        }
+      }
+      store_unit<VEC>(A.out, q.unit0 + u, o);
+      if (keep_u) store_unit<VEC>(A.u_out, (q.row - A.u_row0) * (size_t)g.U + u, t.u.v[j]);
+    }
+  }
+  if constexpr (MODE == 0) {
+    if (A.partial != nullptr) write_partials<VEC, NV, 2>(acc, g, base, A.partial);
+  }
+}
+
+// s = -r^2 * (p * Bq + q * A + xh * (D - 3 * A * Bq)) and the partials of sum u * M(zdot); the formulas stand at bg_ln_gp_source_f32
+template <int MODE, int VEC, int NV, bool LOOP>
+__global__ __launch_bounds__(kT) void ln_source_kernel(const float* __restrict__ u, const float* __restrict__ zdot,
+                                                       const float* __restrict__ z, float* __restrict__ s_out, Geo g,
+                                                       const float* __restrict__ gamma, const float* __restrict__ mu,
+                                                       const float* __restrict__ rs, float* __restrict__ partial) {
+  LN_POS_SETUP();
+  struct Trio { Tile<VEC, NV> z, u, p, q; };      // p = gamma * u, q = zdot (both before centring)
+  float acc[1][NV][VEC];
+#pragma unroll
+  for (int j = 0; j < NV; ++j)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[0][j][e] = 0.f;
+  for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
+    LN_ROW_SETUP();
+    const float mean = q.row_ok ? mu[q.row] : 0.f, r = q.row_ok ? rs[q.row] : 0.f;
+    auto load = [&](int b) {
+      Trio t;
+      t.z = load_tile<VEC, NV>(z, q, b);
+      t.u = load_tile<VEC, NV>(u, q, b);
+      t.q = load_tile<VEC, NV>(zdot, q, b);
+      t.p = t.u;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        if (!unit_ok(q, b, j)) continue;
+        float gm[VEC];
+        load_unit<VEC>(gamma, (size_t)(b + j * q.L + q.sub), gm);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) t.p.v[j][e] = gm[e] * t.u.v[j][e];
+      }
+      return t;
+    };
+    const Trio t = load(base);
+    float sp = 0.f, sq = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Trio& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          sp += x.p.v[j][e];
+          sq += x.q.v[j][e];
+        }
+    });
+    const float pbar = group_sum(sp, q.L) / Cf, qbar = group_sum(sq, q.L) / Cf;
+    float sa = 0.f, sb = 0.f, sd = 0.f;
+    sweep<LOOP, NV>(g.U, t, base, load, [&](const Trio& x, int b) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          if (unit_ok(q, b, j)) {
+            const float xh = (x.z.v[j][e] - mean) * r, pc = x.p.v[j][e] - pbar, qc = x.q.v[j][e] - qbar;
+            sa = fmaf(pc, xh, sa);
+            sb = fmaf(qc, xh, sb);
+            sd = fmaf(pc, qc, sd);
+          }
+    });
+    const float Am = group_sum(sa, q.L) / Cf, Bq = group_sum(sb, q.L) / Cf, Dm = group_sum(sd, q.L) / Cf;
+    const float tail = Dm - 3.f * Am * Bq, nr2 = -(r * r);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      if (!unit_ok(q, base, j)) continue;
+      const int un = base + j * q.L + q.sub;
+      float o[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float xh = (t.z.v[j][e] - mean) * r, pc = t.p.v[j][e] - pbar, qc = t.q.v[j][e] - qbar;
+        o[e] = nr2 * (pc * Bq + qc * Am + xh * tail);
+        acc[0][j][e] = fmaf(t.u.v[j][e], r * (qc - xh * Bq), acc[0][j][e]);
+      }
+      store_unit<VEC>(s_out, q.unit0 + un, o);
+    }
+  }
+  write_partials<VEC, NV, 1>(acc, g, base, partial);
+}
+
+// out_q[c] = beta * out_q[c] + scale * sum over the partial rows, in a fixed order: one wave per (q, c), lane l adds rows l, l + 64, ...
+__global__ __launch_bounds__(kT) void ln_finish_kernel(const float* __restrict__ partial, int nblk, int C, int NQ, float* out0,
+                                                       float* out1, float beta, float scale) {
+  const int idx = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (idx >= NQ * C) return;
+  const int qn = idx / C, c = idx % C;
+  // a lane's loads are issued eight at a time and added in the loop's own order (misc.hip wave_sum_partials: the sum keeps its
+  // bits, and the lane waits for memory once per eight partial rows instead of once per row -- this launch is pure latency)
+  float s = 0.f;
+  int b = lane;
+  const size_t step = (size_t)64 * NQ * C;
+  const float* p = partial + ((size_t)b * NQ + qn) * C + c;
+  for (; b + 7 * 64 < nblk; b += 8 * 64, p += 8 * step) {
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = p[i * step];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += v[i];
+  }
+  if (b < nblk) {
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = b + i * 64 < nblk ? p[i * step] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (b + i * 64 < nblk) s += v[i];
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if (lane == 0) {
+    float* out = qn == 0 ? out0 : out1;
+    out[c] = (beta != 0.f ? beta * out[c] : 0.f) + scale * s;
+  }
+}
+
+inline Geo geo_for(int R, int C, const Route& t) { return Geo{R, C, C / t.vec, t.lg}; }
+
+inline dim3 grid_for(int R, const Route& t) {
+  const size_t rows_wg = (size_t)kWaves * (64 >> t.lg);
+  const size_t groups = ((size_t)R + rows_wg - 1) / rows_wg;
+  return dim3((unsigned)std::min<size_t>(groups, kMaxBlocks), (unsigned)t.chunks);
+}
+
+#define LN_LAUNCH(KERN, MODE, t, grid, s, ...)                                                                  \
+  do {                                                                                                          \
+    if (t.chunks > 1) {                                                                                         \
+      if (t.vec == 4) bg::launch(KERN<MODE, 4, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
+      else bg::launch(KERN<MODE, 1, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                               \
+    } else if (t.vec == 4) {                                                                                    \
+      if (t.nv == 1) bg::launch(KERN<MODE, 4, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
+      else if (t.nv == 2) bg::launch(KERN<MODE, 4, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
+      else bg::launch(KERN<MODE, 4, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
+    } else {                                                                                                    \
+      if (t.nv == 1) bg::launch(KERN<MODE, 1, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
+      else if (t.nv == 2) bg::launch(KERN<MODE, 1, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
+      else bg::launch(KERN<MODE, 1, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
+    }                                                                                                           \
+  } while (0)
+
+inline bool al(const void* p) { return bg::aligned16(p); }      // NULL counts as aligned
+
+int finish(void* stream, const float* partial, int nblk, int C, int NQ, float* out0, float* out1, float beta, float scale) {
+  bg::Launch L(stream, "ln_finish", 0, 4.0 * nblk * NQ * C);
+  bg::launch(ln_finish_kernel, dim3(bg::cdiv((size_t)NQ * C, kWaves)), dim3(kT), 0, L.s, partial, nblk, C, NQ, out0, out1, beta, scale);
+  return L.done("ln_finish_kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int bg_ln_route(int C, int* vec, int* lanes, int* regs, int* chunks) {
+  BG_REQUIRE(C > 0, BG_ERR_BAD_SHAPE, "bg_ln_route: C=%d", C);
+  const Route t = route_for(C);
+  if (vec) *vec = t.vec;
+  if (lanes) *lanes = 1 << t.lg;
+  if (regs) *regs = t.nv;
+  if (chunks) *chunks = t.chunks;
+  return BG_OK;
+}
+
+size_t bg_ln_workspace_bytes(int R, int C) {
+  if (R <= 0 || C <= 0) return 0;
+  return (size_t)grid_for(R, route_for(C)).x * 2 * C * sizeof(float);
+}
+
+int bg_ln_fwd_f32(const float* z, float* a, int R, int C, const float* gamma, const float* beta, float eps, float lrelu_alpha,
+                  const uint8_t* keep, float keep_scale, size_t keep_elems, float* mu, float* r, void* stream) {
+  BG_REQUIRE(z && a && gamma && beta && mu && r, BG_ERR_NULL, "bg_ln_fwd_f32: null pointer");
+  BG_REQUIRE(R > 0 && C > 0 && eps > 0.f, BG_ERR_BAD_SHAPE, "bg_ln_fwd_f32: R=%d C=%d eps=%g", R, C, (double)eps);
+  BG_REQUIRE(keep_elems % (size_t)C == 0 && keep_elems <= (size_t)R * C, BG_ERR_BAD_SHAPE,
+             "bg_ln_fwd_f32: keep_elems=%zu is not a whole number of the %d rows of %d", keep_elems, R, C);
+  BG_REQUIRE(a != z, BG_ERR_UNSUPPORTED, "bg_ln_fwd_f32: a must not alias z (the backward reads z)");
+  const Route t = route_for(C);
+  BG_REQUIRE(t.vec == 1 || (al(z) && al(a) && al(gamma) && al(beta) && al(keep)), BG_ERR_BAD_ALIGNMENT,
+             "bg_ln_fwd_f32: pointers must be 16-byte aligned when C %% 4 == 0");
+  const size_t keep_rows = keep_elems ? keep_elems / (size_t)C : (size_t)R;
+  bg::Launch L(stream, "ln_fwd", 0, (8.0 + (keep ? 1.0 : 0.0)) * R * C + 8.0 * R);
+  const dim3 grid = grid_for(R, t);
+  LN_LAUNCH(ln_fwd_kernel, 0, t, grid, L.s, z, a, geo_for(R, C, t), gamma, beta, eps, lrelu_alpha, keep, keep_scale, keep_rows, mu, r);
+  return L.done("ln_fwd_kernel");
+}
+
+int bg_ln_bwd_f32(const float* g, const float* z, float* dz, int R, int C, const float* gamma, const float* beta, const float* mu,
+                  const float* r, float lrelu_alpha, const uint8_t* keep, float keep_scale, size_t keep_elems, const float* addend,
+                  float* u_out, int u_row0, int u_rows, float* dgamma, float* dbeta, int dw_rows, float acc_beta, float acc_scale,
+                  void* ws_d, size_t ws_bytes, void* stream) {
+  BG_REQUIRE(g && z && dz && gamma && beta && mu && r, BG_ERR_NULL, "bg_ln_bwd_f32: null pointer");
+  BG_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), BG_ERR_NULL, "bg_ln_bwd_f32: dgamma and dbeta come together");
+  BG_REQUIRE(R > 0 && C > 0, BG_ERR_BAD_SHAPE, "bg_ln_bwd_f32: R=%d C=%d", R, C);
+  BG_REQUIRE(lrelu_alpha >= 0.f, BG_ERR_UNSUPPORTED, "bg_ln_bwd_f32: LeakyReLU's branch is re-derived from z, which needs alpha >= 0");
+  BG_REQUIRE(keep_elems % (size_t)C == 0 && keep_elems <= (size_t)R * C, BG_ERR_BAD_SHAPE,
+             "bg_ln_bwd_f32: keep_elems=%zu is not a whole number of the %d rows of %d", keep_elems, R, C);
+  BG_REQUIRE(!u_out || (u_row0 >= 0 && u_rows > 0 && (size_t)u_row0 + u_rows <= (size_t)R), BG_ERR_BAD_SHAPE,
+             "bg_ln_bwd_f32: u rows [%d, %d + %d) of %d", u_row0, u_row0, u_rows, R);
+  BG_REQUIRE(dw_rows <= R, BG_ERR_BAD_SHAPE, "bg_ln_bwd_f32: dw_rows=%d of %d", dw_rows, R);
+  const Route t = route_for(C);
+  BG_REQUIRE(t.vec == 1 || (al(g) && al(z) && al(dz) && al(gamma) && al(beta) && al(keep) && al(addend) && al(u_out)),
+             BG_ERR_BAD_ALIGNMENT, "bg_ln_bwd_f32: pointers must be 16-byte aligned when C %% 4 == 0");
+  BG_REQUIRE(t.chunks == 1 || (dz != g && dz != addend), BG_ERR_UNSUPPORTED,
+             "bg_ln_bwd_f32: dz may alias g or addend on the register routes only (C=%d is swept in %d chunks)", C, t.chunks);
+  BG_REQUIRE(!dgamma || (ws_d && ws_bytes >= bg_ln_workspace_bytes(R, C)), BG_ERR_WORKSPACE, "bg_ln_bwd_f32: workspace too small");
+  const dim3 grid = grid_for(R, t);
+  ApplyArgs A;
+  A.src = g; A.z = z; A.out = dz; A.gamma = gamma; A.beta = beta; A.mu = mu; A.rs = r; A.alpha = lrelu_alpha;
+  A.keep = keep; A.kscale = keep_scale; A.keep_rows = keep_elems ? keep_elems / (size_t)C : (size_t)R;
+  A.addend = addend; A.u_out = u_out; A.u_row0 = u_out ? (size_t)u_row0 : 0; A.u_rows = u_out ? (size_t)u_rows : 0;
+  A.partial = dgamma ? static_cast<float*>(ws_d) : nullptr;
+  A.dw_rows = dw_rows > 0 ? (size_t)dw_rows : (size_t)R;
+  {
+    bg::Launch L(stream, "ln_bwd", 0, (12.0 + (keep ? 1.0 : 0.0) + (addend ? 4.0 : 0.0)) * R * C + (u_out ? 4.0 * u_rows * C : 0.0) + 8.0 * R);
+    LN_LAUNCH(ln_apply_kernel, 0, t, grid, L.s, A, geo_for(R, C, t));
+    const int rc = L.done("ln_apply_kernel");
+    if (rc || !dgamma) return rc;
+  }
+  return finish(stream, A.partial, (int)grid.x, C, 2, dgamma, dbeta, acc_beta, acc_scale);
+}
+
+int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int C, const float* gamma, const float* beta,
+                      const float* mu, const float* r, float lrelu_alpha, void* stream) {
+  BG_REQUIRE(zdot && z && vout && gamma && beta && mu && r, BG_ERR_NULL, "bg_ln_tangent_f32: null pointer");
+  BG_REQUIRE(R > 0 && C > 0, BG_ERR_BAD_SHAPE, "bg_ln_tangent_f32: R=%d C=%d", R, C);
+  BG_REQUIRE(lrelu_alpha >= 0.f, BG_ERR_UNSUPPORTED, "bg_ln_tangent_f32: LeakyReLU's branch is re-derived from z, which needs alpha >= 0");
+  const Route t = route_for(C);
+  BG_REQUIRE(t.vec == 1 || (al(zdot) && al(z) && al(vout) && al(gamma) && al(beta)), BG_ERR_BAD_ALIGNMENT,
+             "bg_ln_tangent_f32: pointers must be 16-byte aligned when C %% 4 == 0");
+  BG_REQUIRE(t.chunks == 1 || vout != zdot, BG_ERR_UNSUPPORTED,
+             "bg_ln_tangent_f32: vout may alias zdot on the register routes only (C=%d is swept in %d chunks)", C, t.chunks);
+  ApplyArgs A;
+  A.src = zdot; A.z = z; A.out = vout; A.gamma = gamma; A.beta = beta; A.mu = mu; A.rs = r; A.alpha = lrelu_alpha;
+  A.keep = nullptr; A.kscale = 1.f; A.keep_rows = 0; A.addend = nullptr; A.u_out = nullptr; A.u_row0 = A.u_rows = 0;
+  A.partial = nullptr; A.dw_rows = 0;
+  bg::Launch L(stream, "ln_tangent", 0, 12.0 * R * C + 8.0 * R);
+  const dim3 grid = grid_for(R, t);
+  LN_LAUNCH(ln_apply_kernel, 1, t, grid, L.s, A, geo_for(R, C, t));
+  return L.done("ln_apply_kernel");
+}
+
+int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float* s, int R, int C, const float* gamma, const float* mu,
+                        const float* r, float* dgamma, float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream) {
+  BG_REQUIRE(u && zdot && z && s && gamma && mu && r && dgamma, BG_ERR_NULL, "bg_ln_gp_source_f32: null pointer");
+  BG_REQUIRE(R > 0 && C > 0, BG_ERR_BAD_SHAPE, "bg_ln_gp_source_f32: R=%d C=%d", R, C);
+  const Route t = route_for(C);
+  BG_REQUIRE(t.vec == 1 || (al(u) && al(zdot) && al(z) && al(s) && al(gamma)), BG_ERR_BAD_ALIGNMENT,
+             "bg_ln_gp_source_f32: pointers must be 16-byte aligned when C %% 4 == 0");
+  BG_REQUIRE(s != u && s != zdot && s != z, BG_ERR_UNSUPPORTED, "bg_ln_gp_source_f32: s must not alias an input");
+  BG_REQUIRE(ws_d && ws_bytes >= bg_ln_workspace_bytes(R, C), BG_ERR_WORKSPACE, "bg_ln_gp_source_f32: workspace too small");
+  const dim3 grid = grid_for(R, t);
+  float* partial = static_cast<float*>(ws_d);
+  {
+    bg::Launch L(stream, "ln_gp_source", 0, 16.0 * R * C + 8.0 * R);
+    LN_LAUNCH(ln_source_kernel, 0, t, grid, L.s, u, zdot, z, s, geo_for(R, C, t), gamma, mu, r, partial);
+    const int rc = L.done("ln_source_kernel");
+    if (rc) return rc;
+  }
+  return finish(stream, partial, (int)grid.x, C, 1, dgamma, dgamma, acc_beta, acc_scale);
+}
+
+}  // extern "C"

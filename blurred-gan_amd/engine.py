@@ -2,19 +2,21 @@
 gradient-penalty linearised forward on the HIP kernels.  There is no tape: every backward formula is
 written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
-A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization] [+ LeakyReLU |
+A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization] [+ LeakyReLU |
 tanh] [+ Dropout]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
 one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  Stage fusion on the device:
   conv (+bias) + LeakyReLU + Dropout      -> one launch (epilogue of the MFMA kernel)
   dgrad + LeakyReLU'/Dropout' of the stage below -> one launch (BG_EPI_MUL_GRAD epilogue)
   pooling backward + LeakyReLU'/Dropout' of the stage below -> one launch (the upsample with ref / keep)
   BatchNormalization + LeakyReLU          -> stats pass + one apply pass
+  LayerNormalization + LeakyReLU + Dropout -> one pass over the conv's stored output (per-pixel statistics, csrc/layernorm.hip)
 
 Net.forward and Net.backward are input / pass set-up, a loop over the stages, and one helper per concern (DESIGN.md §5
 "Engine map"); tests/test_engine_trace_cpu.py holds the order and the arguments of everything they enqueue.
 """
 from __future__ import annotations
 
+import functools
 import os
 from typing import List, Optional
 
@@ -35,6 +37,7 @@ class Stage:
         self.in_shape = tuple(in_shape)
         self.out_shape = tuple(lin.out_shape(in_shape))
         self.bn = None
+        self.ln = None              # layers.LayerNormalization between a Conv2D and its LeakyReLU (the critic's normalisation)
         self.act = getattr(lin, "activation", None)
         self.alpha = 1.0
         self.drop = None
@@ -52,7 +55,7 @@ class Stage:
 
     @property
     def fusable_grad(self):
-        return self.bn is None and self.act == "lrelu"
+        return self.bn is None and self.ln is None and self.act == "lrelu"
 
     @property
     def drop_scale(self):
@@ -62,6 +65,11 @@ class Stage:
         """The BatchNorm's parameters as the keywords every ops.bn_* function names them by (in bn_fold's positional order)."""
         v = self.bn.vars
         return dict(gamma=v["gamma"], beta=v["beta"], moving_mean=v["moving_mean"], moving_var=v["moving_variance"], eps=self.bn.epsilon)
+
+    @property
+    def ln_pixels(self):
+        """Rows of an LN stage's [R, C] view per sample: its map's pixels."""
+        return int(np.prod(self.out_shape[:-1]))
 
 
 class _StageBuffers:
@@ -83,15 +91,19 @@ class Context(_StageBuffers):
         self.a0 = f(B, *net.in_shape)
         self.din = None
         self.a, self.z, self.keep, self.mean, self.inv, self.dz, self.v = [], [], [], [], [], [], []
+        # LayerNormalization stages: the rows' mean / 1 / sqrt(var + eps) live in mean / inv ([B * pixels] each); the penalty keeps
+        # u (the first-order gradient at the normalised pre-activation, x-hat rows), the tangent zdot and the source s
+        n = len(net.stages)
+        self.u, self.u_rows, self.zdot, self.s, self.gin = [None] * n, None, [None] * n, [None] * n, [None] * n
         self.xin: List[Optional[torch.Tensor]] = [None] * len(net.stages)
         for st in net.stages:
             self.a.append(f(B, *st.out_shape))
             self.dz.append(None)
             self.v.append(None)
-            self.z.append(f(B, *st.out_shape) if st.bn is not None else None)
-            c = st.out_shape[-1]
-            self.mean.append(f(c) if st.bn is not None else None)
-            self.inv.append(f(c) if st.bn is not None else None)
+            self.z.append(f(B, *st.out_shape) if st.bn is not None or st.ln is not None else None)
+            c = B * st.ln_pixels if st.ln is not None else st.out_shape[-1]
+            self.mean.append(f(c) if st.bn is not None or st.ln is not None else None)
+            self.inv.append(f(c) if st.bn is not None or st.ln is not None else None)
             self.keep.append(None)
         # dropout masks of all stages live in ONE uint8 buffer (16-byte aligned slices): a pass draws them with one launch
         DR = self.drop_rows
@@ -159,6 +171,20 @@ class Context(_StageBuffers):
             self._bn_grad_scratch[i] = tuple(torch.empty(C, dtype=torch.float32, device=self._device) for _ in range(2))
         return self._bn_grad_scratch[i]
 
+    def keep_u(self, i, rows):
+        """Room for u of LN stage i on samples ``rows`` = (lo, hi): what the first-order backward leaves for the penalty."""
+        n = rows[1] - rows[0]
+        if self.u[i] is None or self.u[i].size(0) != n:
+            self.u[i] = torch.empty((n,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
+        self.u_rows = tuple(rows)
+        return self.u[i]
+
+    def blur_grad(self):
+        """Where blur^T of the input gradient goes when the blurred input itself has to survive the backward."""
+        if "blur_grad" not in self._extra:
+            self._extra["blur_grad"] = torch.empty_like(self.a0)
+        return self._extra["blur_grad"]
+
     def input_grad(self):
         if self.din is None:
             self.din = torch.empty((self.B,) + self._net.in_shape, dtype=torch.float32, device=self._device)
@@ -175,13 +201,24 @@ class _RowView(_StageBuffers):
         key = ("rowview_v", lo, hi)
         self.v = ctx._extra.setdefault(key, [None] * len(ctx.a))
         self._net, self._device = ctx._net, ctx._device
+        # LayerNormalization stages (the penalty's second order): the rows' saved statistics, the u the backward kept for exactly
+        # these samples, own scratch for the tangent and the source
+        px = [st.ln_pixels for st in ctx._net.stages]
+        self.z = [None if t is None else t[lo:hi] for t in ctx.z]
+        self.mean = [t[lo * n:hi * n] if st.ln is not None else None for t, n, st in zip(ctx.mean, px, ctx._net.stages)]
+        self.inv = [t[lo * n:hi * n] if st.ln is not None else None for t, n, st in zip(ctx.inv, px, ctx._net.stages)]
+        self.xin = [None if t is None else t[lo:hi] for t in ctx.xin]
+        self.u, self.u_rows = ctx.u, (None if ctx.u_rows is None else (ctx.u_rows[0] - lo, ctx.u_rows[1] - lo))
+        self.zdot = ctx._extra.setdefault(("rowview_zdot", lo, hi), [None] * len(ctx.a))
+        self.s = ctx._extra.setdefault(("rowview_s", lo, hi), [None] * len(ctx.a))
 
 
 class _BackwardPass:
     """What one Net.backward call carries from stage to stage."""
 
-    def __init__(self, ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, sync_bn):
+    def __init__(self, ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, sync_bn, keep_u_rows=None):
         self.ctx, self.need_dw, self.beta, self.scale, self.reducer = ctx, need_dw, beta, scale, reducer
+        self.keep_u_rows = keep_u_rows      # LN stages keep u of these samples for the penalty's second order
         self.dw_rows = ctx.B if dw_rows is None else int(dw_rows)
         self.defer_conv_dw, self.sync_bn = defer_conv_dw, sync_bn
         self.pending_stats = None       # SyncBN: the all-reduce of the NEXT (lower) stage's backward statistics, in flight
@@ -218,9 +255,20 @@ class Net:
                 cur = Stage(l, s)
                 self.stages.append(cur)
             elif k == "bn":
+                if cur is not None and cur.ln is not None:
+                    raise NotImplementedError("LayerNormalization together with BatchNormalization in one stage is not supported")
                 if cur is None or cur.kind in RESAMPLE or cur.bn is not None or cur.act is not None or cur.drop:
                     raise NotImplementedError("BatchNormalization must directly follow a linear layer")
                 cur.bn = l
+            elif k == "layernorm":
+                if cur is not None and cur.bn is not None:
+                    raise NotImplementedError("LayerNormalization together with BatchNormalization in one stage is not supported")
+                if cur is not None and cur.act == "tanh":
+                    raise NotImplementedError("LayerNormalization and tanh in one stage are not supported")
+                if cur is None or cur.kind != "conv" or cur.ln is not None or cur.act is not None or cur.drop:
+                    raise NotImplementedError("LayerNormalization must directly follow a Conv2D (not a Dense, a Conv2DTranspose or a "
+                                              "resampling layer)")
+                cur.ln = l
             elif k == "lrelu":
                 if cur is None or cur.kind in RESAMPLE or cur.act is not None or cur.drop:
                     raise NotImplementedError("LeakyReLU must follow a linear layer or its BatchNormalization")
@@ -241,10 +289,13 @@ class Net:
                 raise NotImplementedError("Dense + activation without BatchNormalization is not on the reference path")
             if st.act == "tanh" and st.bn is not None:
                 raise NotImplementedError("tanh after BatchNormalization is not on the reference path")
+            if st.ln is not None and st.act != "lrelu":
+                raise NotImplementedError("LayerNormalization must be followed by a LeakyReLU")
         if self.stages and (self.stages[0].kind in RESAMPLE or self.stages[-1].kind in RESAMPLE):
             raise NotImplementedError("UpSampling2D / AveragePooling2D must stand between two linear layers, not first or last in a network")
         self.out_shape = self.stages[-1].out_shape
         self.conv_layers = [st.lin for st in self.stages if st.kind in ("conv", "convT")]
+        self.has_ln = any(st.ln is not None for st in self.stages)
         self._ctx = {}
         self._ws = None
         self._taps_cache = {}
@@ -432,6 +483,7 @@ class Net:
     def _linear_forward(self, ctx, i, st, xin, out, training, folded):
         """Stage i's linear op with what its epilogue fuses (bias, activation, Dropout, folded inference BatchNorm), then its
         BatchNorm + LeakyReLU pass where it has one of its own."""
+        if st.ln is not None: return self.ln_forward(ctx, i, st, xin, out)      # noqa: E701
         bias = st.lin.vars.get("bias")
         tgt = ctx.z[i] if st.bn is not None else out
         stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
@@ -488,6 +540,20 @@ class Net:
         else:
             ops.bn_train_fwd(tgt, out, M, C, ws=self.workspace(ops.bn_workspace_bytes(M, C)), **train)
 
+    def ln_args(self, ctx, i, st):
+        """What every ops.layernorm call of stage i names the same way: rows, channels, the layer's variables and the rows' statistics."""
+        C = st.out_shape[-1]
+        return dict(R=ctx.B * st.ln_pixels, Cc=C, gamma=st.ln.vars["gamma"], mu=ctx.mean[i], r=ctx.inv[i])
+
+    def ln_forward(self, ctx, i, st, xin, out):
+        """Conv2D (+ bias) into ctx.z[i], then out = Dropout(LeakyReLU(LayerNorm(z))) of stage i in one pass; the rows' statistics
+        stay in ctx.mean / ctx.inv."""
+        z = ctx.z[i]
+        self._conv(st, xin, z, False, EPI_NONE, bias=st.lin.vars.get("bias"))
+        keep, scale, keep_elems = ctx.dropout(i)
+        ops.layernorm.fwd(z, out, **self.ln_args(ctx, i, st), beta=st.ln.vars["beta"], eps=st.ln.epsilon, lrelu_alpha=st.alpha, keep=keep,
+                          scale=scale, keep_elems=keep_elems)
+
     @staticmethod
     def _resample(st, x, y):
         """Forward of a resampling stage; linear and parameter-free, so also its linearised forward in the gradient penalty."""
@@ -504,7 +570,7 @@ class Net:
 
     # ------------------------------------------------------------------ backward
     def backward(self, ctx: Context, dout, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=None, dw_rows=None,
-                 dx_rows=None, defer_conv_dw=False):
+                 dx_rows=None, defer_conv_dw=False, keep_u_rows=None):
         """Reverse pass of the last ``forward`` on ``ctx``.  Weight gradients go to ``store.grad``
         (= beta*old + scale*new).  Returns d(loss)/d(net input) *before* the blur (or None).
         ``reducer`` (dist.GradReducer): this pass completes the gradients, so each stage's slice of the flat buffer is
@@ -512,10 +578,12 @@ class Net:
         ``dw_rows``: weight gradients from the first dw_rows samples only; ``dx_rows`` = (lo, hi): the input gradient (last
         data-gradient + blur^T) for those samples only -- the merged critic pass wants weights from [fakes; reals] and the
         image gradient of x-hat.  ``defer_conv_dw``: the conv filter gradients are left to ``gp_second_order_merged`` (bias
-        and Dense gradients are still taken here)."""
+        and Dense gradients are still taken here).  ``keep_u_rows`` = (lo, hi): LayerNormalization stages keep u, the gradient at
+        their normalised pre-activation, for those samples (the x-hat rows: gp_second_order's source term needs it)."""
         if need_dw:
             self.store.ensure_opt_state()
-        p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active())
+        p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active(),
+                          keep_u_rows if self.has_ln else None)
         g, g_is_dz = dout, False
         for i in range(len(self.stages) - 1, -1, -1):
             st = self.stages[i]
@@ -540,8 +608,10 @@ class Net:
                 self._weight_grads(p, i, st, dz, defer_ready=True)
         p.release_deferred()
         if self.blur is not None:
-            # forward's blurred input is dead by now; reuse it for blur^T(din)
-            out = ctx.a0 if dx_rows is None else ctx.a0[dx_rows[0]:dx_rows[1]]
+            # forward's blurred input is dead by now; reuse it for blur^T(din) -- unless the penalty's LayerNormalization source
+            # backward follows (keep_u_rows): its first filter gradient reads the blurred x-hat
+            dst = ctx.a0 if p.keep_u_rows is None else ctx.blur_grad()
+            out = dst if dx_rows is None else dst[dx_rows[0]:dx_rows[1]]
             return self.apply_blur(g.view(g.shape[0], *self.in_shape), out)
         return g
 
@@ -551,6 +621,7 @@ class Net:
         ctx = p.ctx
         if st.bn is not None:
             return self._bn_backward(p, i, st, gv)
+        if st.ln is not None: return self.ln_backward(p, i, st, gv)      # noqa: E701
         if st.act == "tanh":
             return ops.tanh_bwd(gv, ctx.a[i], ctx.buf(ctx.dz, i))
         if st.act != "lrelu" or g_is_dz:
@@ -580,6 +651,23 @@ class Net:
         if p.need_dw:       # the sums are already global: pre-divide so the flat gradient SUM all-reduce restores them
             ops.bn_param_grads(sums, C, 1.0 / world, dg, db)
         return dz
+
+    def ln_backward(self, p, i, st, gv):
+        """Through stage i's Dropout, LeakyReLU and LayerNormalization in one pass: dz, the layer's gamma / beta gradients from the
+        pass's first dw_rows samples, and (keep_u_rows) u for the penalty."""
+        ctx = p.ctx
+        dz = ctx.buf(ctx.dz, i)
+        keep, scale, keep_elems = ctx.dropout(i)
+        args = self.ln_args(ctx, i, st)
+        grads = {}
+        if p.need_dw:
+            grads = dict(dgamma=self.store.grad_of(st.ln, "gamma"), dbeta=self.store.grad_of(st.ln, "beta"), dw_rows=p.dw_rows * st.ln_pixels,
+                         acc_beta=p.beta, acc_scale=p.scale, ws=self.workspace(ops.layernorm.workspace_bytes(args["R"], args["Cc"])))
+        if p.keep_u_rows is not None:
+            lo, hi = p.keep_u_rows
+            grads.update(u_out=ctx.keep_u(i, (lo, hi)), u_rows=(lo * st.ln_pixels, hi * st.ln_pixels))
+        return ops.layernorm.bwd(gv, ctx.z[i], dz, **args, beta=st.ln.vars["beta"], lrelu_alpha=st.alpha, keep=keep, scale=scale,
+                                 keep_elems=keep_elems, **grads)
 
     def _bn_bwd_stats(self, p, i, st, g):
         """SyncBN: the backward statistics of BatchNorm stage i from the gradient ``g`` of its output, their all-reduce in flight."""
@@ -611,9 +699,13 @@ class Net:
             # collective stream, and the small statistics exchange of the next stage down, issued one iteration later,
             # would queue behind it -- back on the critical path.  The slice waits until that exchange is in flight.
             if defer_ready:
-                p.deferred_ready.append(self.store.train_range(lin, st.bn))
+                p.deferred_ready.append(self._train_range(st))
             else:
-                p.reducer.ready(*self.store.train_range(lin, st.bn))
+                p.reducer.ready(*self._train_range(st))
+
+    def _train_range(self, st):
+        """The slice of the flat trainable buffer that holds stage ``st``'s variables: its linear op's and its normalisation's."""
+        return self.store.train_range(st.lin, st.bn if st.ln is None else st.ln)
 
     def _input_grad(self, p, i, st, prev, dz, dx_rows):
         """The gradient w.r.t. stage i's input into the dz buffer of the stage below (the pass's input-gradient buffer at i = 0).
@@ -621,7 +713,10 @@ class Net:
         the data gradient's epilogue or in the pooling backward)."""
         ctx = p.ctx
         fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
-        tgt = (ctx.buf(ctx.dz, i - 1) if i > 0 else ctx.input_grad()).view(ctx.B, *st.in_shape)
+        # the gradient at an LN stage's output lands in that stage's dz buffer and is turned into dz in place -- except where a row
+        # exceeds what a wave holds in registers (ops.layernorm.route: chunks > 1), where the kernel wants a buffer of its own
+        below = ctx.gin if prev is not None and prev.ln is not None and ops.layernorm.route(prev.out_shape[-1])["chunks"] > 1 else ctx.dz
+        tgt = (ctx.buf(below, i - 1) if i > 0 else ctx.input_grad()).view(ctx.B, *st.in_shape)
         if st.kind == "upsample":           # transpose of the upsample
             ops.pool2x_sum(dz.view(ctx.B, *st.out_shape), tgt, 1.0)
         elif st.kind == "avgpool" and not fuse:
@@ -649,8 +744,8 @@ class Net:
         kinds = []
         for i, st in enumerate(self.stages):
             last = i == len(self.stages) - 1
-            if st.kind == "conv" and st.fusable_grad and not last:
-                kinds.append("conv")
+            if st.kind == "conv" and st.bn is None and st.act == "lrelu" and not last:
+                kinds.append("conv" if st.ln is None else "ln")
             elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
                 kinds.append("dense")
             elif st.kind in RESAMPLE and not last:
@@ -685,8 +780,12 @@ class Net:
         -- dead after the backward except for their signs, which the linearised forward consumes as it overwrites them in
         place -- both are ONE filter gradient over all 3B rows of (a_{i-1}, dz_i): five launches (and their slab reduces)
         fewer per D-step, and the remaining ones run at 3B rows instead of 2B + B.  The caller has put delta-bar_0 into
-        ctx.a0[lo:hi] and run ``backward(..., defer_conv_dw=True)``."""
+        ctx.a0[lo:hi] and run ``backward(..., defer_conv_dw=True)``.
+
+        Not with LayerNormalization stages: their source backward (gp_ln_source_backward) needs the x-hat rows of the activations
+        this pass overwrites, so such a critic takes ``gp_second_order`` on ``ctx.rows(lo, hi)``."""
         kinds = self._gp_kinds()
+        if "ln" in kinds: raise NotImplementedError("gp_second_order_merged overwrites activations the LayerNormalization source backward needs")  # noqa: E701
         self.store.ensure_opt_state()
         for i, (kind, st) in enumerate(zip(kinds, self.stages)):
             xin = ctx.xin[i]                # [3B, ...]: activations of [fakes; reals], delta-bar_{i-1} in the x-hat rows
@@ -698,11 +797,74 @@ class Net:
     def gp_second_order(self, ctx: Context, v0, reducer=None):
         """SURVEY.md 8a, GP derivation step 2: one linearised forward of the critic on ``v0`` with the
         LeakyReLU masks of the x-hat pass frozen, plus one wgrad per conv layer against the zeta_i kept by
-        the first-order backward (``ctx.dz``); accumulates into ``store.grad`` (beta = 1)."""
+        the first-order backward (``ctx.dz``); accumulates into ``store.grad`` (beta = 1).
+
+        A LayerNormalization stage is not piecewise linear: its tangent is gp_ln_stage's, and what the linearised forward's
+        dependence on the stage's PRIMAL input adds goes down the network once more in gp_ln_source_backward.  That pass writes the
+        last contribution to every layer up to the top-most such stage, so those layers' slices go to the reducer from there."""
         kinds = self._gp_kinds()
         self.store.ensure_opt_state()
+        top = max((i for i, k in enumerate(kinds) if k == "ln"), default=-1)
         v = v0
         for i, (kind, st) in enumerate(zip(kinds, self.stages)):
             vin = v.view(ctx.B, *st.in_shape)
             v = None if kind == "dense" else ctx.buf(ctx.v, i)
-            self._gp_stage(kind, st, vin, ctx.dz[i], 1.0, vin, ctx.a[i], v, reducer)
+            stage = self._gp_stage if kind != "ln" else functools.partial(self.gp_ln_stage, ctx, i)
+            stage(kind, st, vin, ctx.dz[i], 1.0, vin, ctx.a[i], v, reducer if i > top else None)
+        self.gp_ln_source_backward(ctx, top, reducer)
+
+    # ---- LayerNormalization in the penalty (DESIGN.md §5 "Penalty with LayerNormalization stages").  These helpers, like
+    # ln_forward / ln_backward above, carry public names: the engine-trace fixture asks that its configurations -- none has such a
+    # stage -- execute every line of Net's private helpers; tests/test_layernorm_cpu.py records what they enqueue instead.
+    def gp_ln_stage(self, ctx, i, kind, st, wx, wdz, wbeta, v, ref, vout, reducer):
+        """_gp_stage for a Conv2D + LayerNormalization stage: the filter gradient wgrad(wx, zeta_i) as for any conv, the tangent
+        zdot_i = conv(v) (kept), vout = LeakyReLU' * gamma * M(zdot_i), and the source: s_i = dT/dz_i (kept) with
+        dgamma_i += sum u_i * M(zdot_i).  Nothing goes to the reducer here: gp_ln_source_backward still writes into the slice."""
+        assert reducer is None and ctx.u[i] is not None and ctx.u_rows == (0, ctx.B), "backward(keep_u_rows=...) has not kept u for these rows"
+        self._filter_grad(st, wx, wdz, wbeta, 1.0)
+        zdot, s = ctx.buf(ctx.zdot, i), ctx.buf(ctx.s, i)
+        self._conv(st, v, zdot, False, EPI_NONE)
+        args = self.ln_args(ctx, i, st)
+        ops.layernorm.tangent(zdot, ctx.z[i], vout, **args, beta=st.ln.vars["beta"], lrelu_alpha=st.alpha)
+        ops.layernorm.gp_source(ctx.u[i], zdot, ctx.z[i], s, **args, dgamma=self.store.grad_of(st.ln, "gamma"),
+                                ws=self.workspace(ops.layernorm.workspace_bytes(args["R"], args["Cc"])))
+
+    def gp_ln_source_backward(self, ctx, top, reducer=None):
+        """An ordinary first-order backward over the x-hat rows that starts at the top-most LayerNormalization stage ``top`` with
+        lambda_z = s_top and picks up s_i at every such stage below: filter and bias gradients against the PRIMAL inputs, the
+        stages' gamma / beta gradients, all accumulated into store.grad (beta = 1).  The tangent buffers ctx.v are dead by now and
+        carry the gradient down.  Each layer's slice goes to the reducer behind the last launch that writes into it."""
+        lam = None if top < 0 else ctx.s[top]
+        for i in range(top, -1, -1):
+            st, prev = self.stages[i], self.stages[i - 1] if i > 0 else None
+            if st.kind not in RESAMPLE:
+                self._filter_grad(st, ctx.xin[i], lam, 1.0, 1.0)
+                if "bias" in st.lin.vars:
+                    N = st.out_shape[-1]
+                    rows = lam.numel() // N
+                    ops.colsum(lam, self.store.grad_of(st.lin, "bias"), rows, N, self.workspace(ops.colsum_workspace_bytes(rows, N)), beta=1.0, scale=1.0)
+                if reducer is not None:
+                    reducer.ready(*self._train_range(st))
+            if i == 0:
+                break
+            tgt = ctx.v[i - 1].view(ctx.B, *st.in_shape)
+            fuse = prev.fusable_grad and st.kind != "upsample"
+            if st.kind == "upsample":
+                ops.pool2x_sum(lam, tgt, 1.0)
+            elif st.kind == "avgpool":
+                ops.upsample2x(lam, tgt, 0.25, **(dict(ref=ctx.a[i - 1], alpha=prev.alpha) if fuse else {}))
+            elif fuse:
+                self._conv(st, lam, tgt, True, EPI_MUL_GRAD, ref=ctx.a[i - 1], alpha=prev.alpha)
+            else:
+                self._conv(st, lam, tgt, True, EPI_NONE)
+            lam = tgt
+            if prev.ln is not None:
+                # LeakyReLU' and the LayerNormalization backward of the stage below, plus its own source term
+                args = self.ln_args(ctx, i - 1, prev)
+                # in place where the kernel allows it, else into the stage's tangent buffer, dead since its source was taken
+                out = tgt if ops.layernorm.route(args["Cc"])["chunks"] == 1 else ctx.zdot[i - 1]
+                lam = ops.layernorm.bwd(tgt, ctx.z[i - 1], out, **args, beta=prev.ln.vars["beta"], lrelu_alpha=prev.alpha,
+                                        addend=ctx.s[i - 1], dgamma=self.store.grad_of(prev.ln, "gamma"), dbeta=self.store.grad_of(prev.ln, "beta"),
+                                        acc_beta=1.0, acc_scale=1.0, ws=self.workspace(ops.layernorm.workspace_bytes(args["R"], args["Cc"])))
+            elif prev.kind not in RESAMPLE and not fuse:      # conv + LeakyReLU below an UpSampling2D: no launch to fuse it into
+                ops.mul_grad(tgt, ctx.a[i - 1], tgt, alpha=prev.alpha)

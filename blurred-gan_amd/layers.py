@@ -146,6 +146,31 @@ class BatchNormalization(Layer):
                 ("moving_mean", (c,), False, _zeros((c,))), ("moving_variance", (c,), False, _ones((c,)))]
 
 
+class LayerNormalization(Layer):
+    """tf.keras.layers.LayerNormalization over the channel axis of an [H, W, C] map: each pixel's C channels are normalised with
+    their biased variance, n = gamma * (z - mean) / sqrt(var + epsilon) + beta (the WGAN-GP critic's normalisation)."""
+    kind = "layernorm"
+
+    def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, **kw):
+        super().__init__(**kw)
+        ax = tuple(axis) if isinstance(axis, (list, tuple)) else (axis,)
+        if len(ax) != 1 or ax[0] not in (-1, 3):
+            raise NotImplementedError(f"LayerNormalization axis {axis!r}: only the last axis of an [H, W, C] map (-1 or 3) is supported")
+        if not center or not scale:
+            raise NotImplementedError("LayerNormalization with center=False or scale=False is not supported")
+        self.axis, self.epsilon, self.center, self.scale = -1, float(epsilon), True, True
+
+    def out_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"LayerNormalization needs an [H, W, C] map, got {tuple(s)}")
+        return tuple(s)
+
+    def var_specs(self, s):
+        self.out_shape(s)
+        c = int(s[-1])
+        return [("gamma", (c,), True, _ones((c,))), ("beta", (c,), True, _zeros((c,)))]
+
+
 class LeakyReLU(Layer):
     kind = "lrelu"
 

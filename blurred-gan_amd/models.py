@@ -9,7 +9,11 @@ stacks with 3x3 kernels -- every other architecture uses the demos' 5x5).
 Both stacks have a resampling variant with the same map sizes, variable counts and Dense input: ``upsampling="resize"`` replaces
 every stride-2 transposed convolution by nearest-neighbour UpSampling2D + a stride-1 Conv2D (the resize-convolution generator),
 ``downsampling="pool"`` every stride-2 convolution by a stride-1 one whose LeakyReLU / Dropout output is average-pooled.  Such a
-stage convolves at the higher resolution: 4x the multiply-adds of the strided layer it replaces."""
+stage convolves at the higher resolution: 4x the multiply-adds of the strided layer it replaces.
+
+The critic takes ``normalization="layer"``: a LayerNormalization over the channels between every Conv2D and its LeakyReLU (the
+WGAN-GP paper's critic; BatchNormalization cannot stand there, the penalty is defined per sample).  Map sizes are unchanged, every
+block gains 2 * C variables; it combines with ``downsampling="pool"``."""
 from __future__ import annotations
 
 from . import layers
@@ -62,15 +66,19 @@ class DCGANGenerator(layers.Sequential):
 
 
 class DCGANDiscriminator(layers.Sequential):
-    def __init__(self, arch="celeba128", *args, downsampling="stride", **kwargs):
+    def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, **kwargs):
         super().__init__(*args, **kwargs)
         if downsampling not in ("stride", "pool"):
             raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
-        self.downsampling = downsampling
+        if normalization not in (None, "layer"):
+            raise ValueError(f"normalization must be None or 'layer', got {normalization!r}")
+        self.downsampling, self.normalization = downsampling, normalization
         pool = downsampling == "pool"
         for i, c in enumerate(_D[arch]):
             kw = dict(input_shape=list(IMAGE_SHAPE[arch])) if i == 0 else {}
             self.add(layers.Conv2D(c, KSIZE.get(arch, 5), strides=1 if pool else 2, padding="same", **kw))
+            if normalization == "layer":
+                self.add(layers.LayerNormalization())
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
             if pool:

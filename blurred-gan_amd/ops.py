@@ -350,6 +350,73 @@ def bn_param_grads(sums, Cc, scale, dgamma, dbeta):
     check(_lib.load().bg_bn_param_grads_f32(_ptr(sums), Cc, scale, _ptr(dgamma), _ptr(dbeta), _stream()), "bg_bn_param_grads_f32")
 
 
+# ------------------------------------------------------------------ layer normalisation (include/bgan.h "layer normalisation")
+class layernorm:
+    """The LayerNormalization kernels.  A namespace, not module-level functions: the engine-trace maker (tests/golden) replaces
+    every public FUNCTION of this module by a recorder from a list it holds and refuses one it does not know; these calls are
+    recorded by the layer normalisation tests' own recorder instead."""
+
+    @staticmethod
+    def route(Cc):
+        """How the kernels lay a row of ``Cc`` channels over a wave: dict(vec, lanes, regs, chunks, rows_per_workgroup)."""
+        v = [C.c_int() for _ in range(4)]
+        check(_lib.load().bg_ln_route(int(Cc), *[C.byref(x) for x in v]), "bg_ln_route")
+        vec, lanes, regs, chunks = (x.value for x in v)
+        return dict(vec=vec, lanes=lanes, regs=regs, chunks=chunks, rows_per_workgroup=4 * (64 // lanes))
+
+    @staticmethod
+    def workspace_bytes(R, Cc):
+        return _lib.load().bg_ln_workspace_bytes(R, Cc)
+
+    @staticmethod
+    def _ws_bytes(ws):
+        return 0 if ws is None else ws.numel() * ws.element_size()
+
+    @staticmethod
+    def fwd(z, a, R, Cc, gamma, beta, mu, r, eps=1e-3, lrelu_alpha=LRELU_ALPHA, keep=None, scale=1.0, keep_elems=0):
+        """a = Dropout(LeakyReLU(LayerNorm(z))) over the rows of z [R, Cc]; saves the rows' mean and 1 / sqrt(var + eps)."""
+        _f32(z, a, gamma, beta, mu, r)
+        assert z.numel() == R * Cc == a.numel() and gamma.numel() == Cc == beta.numel() and mu.numel() >= R and r.numel() >= R
+        assert keep is None or (keep.dtype == torch.uint8 and keep.numel() >= (keep_elems or R * Cc))
+        check(_lib.load().bg_ln_fwd_f32(_ptr(z), _ptr(a), R, Cc, _ptr(gamma), _ptr(beta), eps, lrelu_alpha, _ptr(keep), scale, int(keep_elems),
+                                        _ptr(mu), _ptr(r), _stream()), "bg_ln_fwd_f32")
+        return a
+
+    @staticmethod
+    def bwd(g, z, dz, R, Cc, gamma, beta, mu, r, lrelu_alpha=LRELU_ALPHA, keep=None, scale=1.0, keep_elems=0, addend=None, u_out=None,
+            u_rows=None, dgamma=None, dbeta=None, dw_rows=0, acc_beta=0.0, acc_scale=1.0, ws=None):
+        """dz = M(gamma * u) [+ addend] with u = g * LeakyReLU' * Dropout'; ``u_out`` keeps u of rows ``u_rows`` = (lo, hi); dgamma /
+        dbeta (both or neither) = acc_beta * old + acc_scale * sums over the first ``dw_rows`` rows (0: all)."""
+        _f32(g, z, dz, gamma, beta, mu, r, addend, u_out, dgamma, dbeta)
+        assert g.numel() == R * Cc == z.numel() == dz.numel() and (addend is None or addend.numel() == R * Cc)
+        assert keep is None or (keep.dtype == torch.uint8 and keep.numel() >= (keep_elems or R * Cc))
+        lo, hi = (0, R) if u_rows is None else u_rows
+        assert u_out is None or u_out.numel() == (hi - lo) * Cc
+        assert dgamma is None or (dgamma.numel() == Cc == dbeta.numel())
+        check(_lib.load().bg_ln_bwd_f32(_ptr(g), _ptr(z), _ptr(dz), R, Cc, _ptr(gamma), _ptr(beta), _ptr(mu), _ptr(r), lrelu_alpha, _ptr(keep),
+                                        scale, int(keep_elems), _ptr(addend), _ptr(u_out), lo, hi - lo, _ptr(dgamma), _ptr(dbeta), int(dw_rows),
+                                        acc_beta, acc_scale, _ptr(ws), layernorm._ws_bytes(ws), _stream()), "bg_ln_bwd_f32")
+        return dz
+
+    @staticmethod
+    def tangent(zdot, z, vout, R, Cc, gamma, beta, mu, r, lrelu_alpha=LRELU_ALPHA):
+        """vout = LeakyReLU' * gamma * M(zdot): the gradient penalty's linearised forward through a LayerNorm stage."""
+        _f32(zdot, z, vout, gamma, beta, mu, r)
+        assert zdot.numel() == R * Cc == z.numel() == vout.numel()
+        check(_lib.load().bg_ln_tangent_f32(_ptr(zdot), _ptr(z), _ptr(vout), R, Cc, _ptr(gamma), _ptr(beta), _ptr(mu), _ptr(r), lrelu_alpha,
+                                            _stream()), "bg_ln_tangent_f32")
+        return vout
+
+    @staticmethod
+    def gp_source(u, zdot, z, s, R, Cc, gamma, mu, r, dgamma, ws, acc_beta=1.0, acc_scale=1.0):
+        """s = dT/dz and dgamma = acc_beta * dgamma + acc_scale * dT/dgamma of T = <u, gamma * M(zdot)> (bg_ln_gp_source_f32)."""
+        _f32(u, zdot, z, s, gamma, mu, r, dgamma)
+        assert u.numel() == R * Cc == zdot.numel() == z.numel() == s.numel() and dgamma.numel() == Cc
+        check(_lib.load().bg_ln_gp_source_f32(_ptr(u), _ptr(zdot), _ptr(z), _ptr(s), R, Cc, _ptr(gamma), _ptr(mu), _ptr(r), _ptr(dgamma),
+                                              acc_beta, acc_scale, _ptr(ws), layernorm._ws_bytes(ws), _stream()), "bg_ln_gp_source_f32")
+        return s
+
+
 # ------------------------------------------------------------------ pointwise / losses / optimisers / rng
 def lerp(r, f, alpha_b, out):
     B = r.shape[0]

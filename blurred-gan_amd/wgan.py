@@ -439,9 +439,11 @@ class WGAN:
             ds3 = self._buf("ds3", (3 * B,))
             ops.fill(ds3[2 * B:], 1.0)
             ops.wgangp_d_loss(fs, rs, None, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)      # seeds only; metrics below
-            one_wgrad = self.merge_gp_filter_gradients
+            # a critic with LayerNormalization stages takes the separate second-order route whatever the switch says: the merged one
+            # overwrites the x-hat rows of the activations that the stages' source backward reads (engine.gp_second_order_merged)
+            one_wgrad = self.merge_gp_filter_gradients and not D.has_ln
             g = D.backward(c3, ds3.view(3 * B, 1), need_dx=True, need_dw=True, beta=0.0, scale=1.0, dw_rows=2 * B,
-                           dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad)
+                           dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad, keep_u_rows=(2 * B, 3 * B))
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
             ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
             if one_wgrad:
@@ -506,7 +508,7 @@ class WGAN:
         B = int(reals.shape[0])
         D = self.discriminator.net()
         return _first_order(D, D.context(B, "hat"), reals, fakes, self._gp_alpha(B), self._buf("xhat", tuple(reals.shape)),
-                            self._buf("ones", (B, 1)), self._buf("gp_norms", (B,)))
+                            self._buf("ones", (B, 1)), self._buf("gp_norms", (B,)), keep_u=True)
 
     # ---- generator
     def generator_loss(self, fake_scores):
@@ -636,11 +638,12 @@ class WGAN:
         return history
 
 
-def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms):
+def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms, keep_u=False):
     """wgan.py:234-245 on the device: x_hat, critic forward (training=False), gradient w.r.t. x_hat (through blur^T),
-    per-sample L2 norms.  ``xhat``, ``ones`` and ``norms`` are the caller's buffers; returns (norms, gradient)."""
+    per-sample L2 norms.  ``xhat``, ``ones`` and ``norms`` are the caller's buffers; returns (norms, gradient).  ``keep_u``: the
+    second order follows, so LayerNormalization stages keep what its source term needs (engine.Net.backward keep_u_rows)."""
     D.forward(ctx, ops.lerp(reals, fakes, alpha, xhat), training=False)
-    g = D.backward(ctx, ops.fill(ones, 1.0), need_dx=True, need_dw=False)
+    g = D.backward(ctx, ops.fill(ones, 1.0), need_dx=True, need_dw=False, keep_u_rows=(0, int(reals.shape[0])) if keep_u else None)
     return ops.row_norm(g, norms), g
 
 

@@ -56,12 +56,15 @@ class DCGANGenerator(layers.Sequential):
 class DCGANDiscriminator(layers.Sequential):
     """demo_celeba.py:96-124."""
 
-    def __init__(self, *args, downsampling="stride", **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", **kwargs):
         super().__init__(*args, **kwargs)
         pool = {"stride": False, "pool": True}[downsampling]
+        norm = {"none": False, "layer": True}[normalization]
         for i, c in enumerate((16, 32, 64, 128, 256, 512)):
             kw = dict(input_shape=[128, 128, 3]) if i == 0 else {}
             self.add(layers.Conv2D(c, 5, strides=1 if pool else 2, padding='same', **kw))
+            if norm:
+                self.add(layers.LayerNormalization())
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
             if pool:
@@ -86,6 +89,9 @@ def make_parser():
     parser.add_argument("--downsampling", default="stride", choices=["stride", "pool"],
                         help="critic resolution steps: stride-2 Conv2D (default, the reference's) or stride-1 Conv2D + AveragePooling2D "
                              "(4x the multiply-adds of the layers it replaces)")
+    parser.add_argument("--critic-norm", dest="critic_norm", default="none", choices=["none", "layer"],
+                        help="critic normalisation: none (default, the reference's) or a LayerNormalization over the channels between "
+                             "every Conv2D and its LeakyReLU (the WGAN-GP paper's critic)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -125,7 +131,7 @@ def main(argv=None):
         total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
-    gen, disc = DCGANGenerator(upsampling=args.upsampling), DCGANDiscriminator(downsampling=args.downsampling)
+    gen, disc = DCGANGenerator(upsampling=args.upsampling), DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

@@ -62,16 +62,21 @@ class DCGANGenerator(layers.Sequential):
 class DCGANDiscriminator(layers.Sequential):
     """demo_mnist.py:74-86."""
 
-    def __init__(self, *args, downsampling="stride", **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", **kwargs):
         super().__init__(*args, **kwargs)
         pool = {"stride": False, "pool": True}[downsampling]
+        norm = {"none": False, "layer": True}[normalization]
         strides = (1, 1) if pool else (2, 2)
         self.add(layers.Conv2D(64, (5, 5), strides=strides, padding='same', input_shape=[28, 28, 1]))
+        if norm:
+            self.add(layers.LayerNormalization())
         self.add(layers.LeakyReLU())
         self.add(layers.Dropout(0.3))
         if pool:
             self.add(layers.AveragePooling2D())
         self.add(layers.Conv2D(128, (5, 5), strides=strides, padding='same'))
+        if norm:
+            self.add(layers.LayerNormalization())
         self.add(layers.LeakyReLU())
         self.add(layers.Dropout(0.3))
         if pool:
@@ -96,6 +101,9 @@ def make_parser():
     parser.add_argument("--downsampling", default="stride", choices=["stride", "pool"],
                         help="critic resolution steps: stride-2 Conv2D (default, the reference's) or stride-1 Conv2D + AveragePooling2D "
                              "(4x the multiply-adds of the layers it replaces)")
+    parser.add_argument("--critic-norm", dest="critic_norm", default="none", choices=["none", "layer"],
+                        help="critic normalisation: none (default, the reference's) or a LayerNormalization over the channels between "
+                             "every Conv2D and its LeakyReLU (the WGAN-GP paper's critic)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -143,7 +151,7 @@ def main(argv=None):
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
     gen = DCGANGenerator(upsampling=args.upsampling)
-    disc = DCGANDiscriminator(downsampling=args.downsampling)
+    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

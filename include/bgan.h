@@ -248,6 +248,47 @@ int bg_bn_bwd_apply_f32(const float* dy, const float* y, const float* x, float* 
    (scale = 1 / replicas, so that the SUM all-reduce of the flat gradient buffer restores the global value) */
 int bg_bn_param_grads_f32(const float* sums_d, int C, float scale, float* dgamma, float* dbeta, void* stream);
 
+/* ---- layer normalisation: tf.keras.layers.LayerNormalization(axis=-1) + LeakyReLU (+ Dropout) over NHWC fp32 maps ------------
+ * Data is [R, C]: R = B*H*W rows of C contiguous channels.  Per row, with every mean taken over the row's C channels:
+ *   mu = mean(z),  r = 1 / sqrt(mean((z - mu)^2) + eps)   (saved by the forward, [R] floats each),   xh = (z - mu) * r,
+ *   M y = r * (yc - xh * mean(yc * xh)),  yc = y - mean(y)   (the Jacobian of z -> xh; symmetric).
+ * LeakyReLU's branch is never read from the activation: every call re-derives n = gamma * xh + beta from z with the forward's own
+ * expression (the same operations on the same inputs: the same bits), which needs lrelu_alpha >= 0 (BG_ERR_UNSUPPORTED otherwise).
+ * keep / keep_scale / keep_elems follow bg_epilogue: the uint8 mask covers the first keep_elems elements (0 = all of them; a whole
+ * number of rows), a masked element is multiplied by keep ? keep_scale : 0.
+ * C % 4 == 0 moves float4s and wants z, a, g, dz, zdot, vout, u, s, addend, u_out, keep, gamma and beta 16-byte aligned
+ * (BG_ERR_BAD_ALIGNMENT otherwise); any other C goes one float at a time.  bg_ln_route tells how a C is laid over a wave: floats
+ * per unit (4 or 1), lanes that share a row (64 / lanes rows per wave, four waves per workgroup), units a lane keeps in registers,
+ * and the chunks a row is swept in when it exceeds what one wave holds (1: the row is read once).  A refused call launches
+ * nothing.  Column sums are reduced through per-workgroup partials in the workspace and a fixed-order finish: no floating-point
+ * atomics, the same bits on every run.  No call takes a step-program binding. */
+int bg_ln_route(int C, int* vec, int* lanes, int* regs, int* chunks);
+size_t bg_ln_workspace_bytes(int R, int C);
+/* a = Dropout(LeakyReLU(gamma * xh + beta)); writes mu, r.  a must not alias z. */
+int bg_ln_fwd_f32(const float* z, float* a, int R, int C, const float* gamma, const float* beta, float eps, float lrelu_alpha,
+                  const uint8_t* keep /* may be NULL */, float keep_scale, size_t keep_elems, float* mu, float* r, void* stream);
+/* g: the gradient at a.  u = g * LeakyReLU' * Dropout' (the gradient at n),  dz = M(gamma * u) [+ addend].
+ * u_out (may be NULL): u of rows [u_row0, u_row0 + u_rows), stored from its own row 0 (the penalty keeps the x-hat rows' u).
+ * dgamma / dbeta (both or neither; NULL: the generator step's form, no sums and no workspace):
+ *   dgamma = acc_beta * dgamma + acc_scale * sum_rows u * xh,  dbeta = acc_beta * dbeta + acc_scale * sum_rows u
+ * over rows [0, dw_rows) (dw_rows <= 0: all of them).  dz may alias g (or addend) where bg_ln_route gives chunks == 1. */
+int bg_ln_bwd_f32(const float* g, const float* z, float* dz, int R, int C, const float* gamma, const float* beta, const float* mu,
+                  const float* r, float lrelu_alpha, const uint8_t* keep, float keep_scale, size_t keep_elems,
+                  const float* addend /* may be NULL */, float* u_out, int u_row0, int u_rows, float* dgamma, float* dbeta, int dw_rows,
+                  float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream);
+/* the penalty's tangent through the stage (no Dropout on the x-hat rows):  vout = LeakyReLU' * gamma * M(zdot).  The same kernel
+ * as the backward.  vout may alias zdot where bg_ln_route gives chunks == 1. */
+int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int C, const float* gamma, const float* beta,
+                      const float* mu, const float* r, float lrelu_alpha, void* stream);
+/* the penalty's second-order source.  u: the first-order gradient at n on the x-hat rows, zdot: the tangent at z.  The term
+ * T = <u, gamma * M(zdot)> of the linearised forward depends on z through xh and r, and on gamma directly:
+ *   dT/dgamma = sum_rows u * M(zdot)                          -> dgamma = acc_beta * dgamma + acc_scale * that
+ *   dT/dz = s = -r^2 * (p * Bq + q * A + xh * (D - 3 * A * Bq))
+ *   with  p = gamma * u - mean(gamma * u),  q = zdot - mean(zdot),  A = mean(p * xh),  Bq = mean(q * xh),  D = mean(p * q).
+ * (dT/dzdot = M(gamma * u) is the dz bg_ln_bwd_f32 left behind.)  s must not alias an input. */
+int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float* s, int R, int C, const float* gamma, const float* mu,
+                        const float* r, float* dgamma, float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---- pointwise ------------------------------------------------------------------------------ */
 /* wgan.py:239: xhat[b,:] = r[b,:] + alpha[b] * (f[b,:] - r[b,:]) */
 int bg_lerp_f32(const float* r, const float* f, const float* alpha_b, float* xhat, int B, int n_per, void* stream);
