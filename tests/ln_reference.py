@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import blurred_gan_amd as bg
-from blurred_gan_amd import models
+from blurred_gan_amd import layers, models
 from helpers import rel_l2
 from oracle import torch_ref as TR
 
@@ -154,11 +154,16 @@ def draw(disc, B, latent, rng):
     return dict(z_d=u(B, latent), z_g=u(B, latent), alpha=u(B), mask_fake=mk(), mask_real=mk())
 
 
-def make_gan(arch, B, seed, up="transpose", down="stride", normalization="layer", std=None, gbs=None, device=None, **kw):
+def make_gan(arch, B, seed, up="transpose", down="stride", normalization="layer", std=None, gbs=None, device=None, disc=None, **kw):
+    """``disc``: a ready (unbuilt) critic for ``arch``'s images, or a callable that returns one (tests/ln_critics.py), in place of
+    models.DCGANDiscriminator(arch, down, normalization); it is made after the seed is set and the generator exists, as that one is."""
     bg.set_seed(seed)
     rng = np.random.default_rng(seed)
     gen = models.DCGANGenerator(arch=arch, upsampling=up)
-    disc = models.DCGANDiscriminator(arch=arch, downsampling=down, normalization=normalization)
+    if disc is None:
+        disc = models.DCGANDiscriminator(arch=arch, downsampling=down, normalization=normalization)
+    elif callable(disc) and not isinstance(disc, layers.Sequential):
+        disc = disc()
     if device is not None:              # reference-only use (seed selection on a host without a GPU)
         gen.build(device), disc.build(device)
     randomize(gen, rng), randomize(disc, rng)
