@@ -79,6 +79,11 @@ SIGNATURES = {
     "bg_ln_bwd_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _f, _z, _p, _p, _i, _i, _p, _p, _i, _f, _f, _p, _z, _p]),
     "bg_ln_tangent_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p]),
     "bg_ln_gp_source_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _f, _p, _z, _p]),
+    "bg_spectral_route": (_i, [_i, _i, _i] + [C.POINTER(_i)] * 8),
+    "bg_spectral_workspace_bytes": (_z, [_p, _i]),
+    "bg_spectral_power_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _z, _p]),
+    "bg_spectral_scale_f32": (_i, [_p, _p, _p, _p, _p, _i, _p]),
+    "bg_spectral_grad_f32": (_i, [_p, _p, _p, _p, _p, _i, _p, _z, _p]),
     "bg_lerp_f32":(_i, [_p, _p, _p, _p, _i, _i, _p]),
     "bg_row_norm_f32": (_i, [_p, _p, _i, _i, _p]),
     "bg_gp_seed_f32": (_i, [_p, _p, _f, _p, _i, _i, _p]),
@@ -133,6 +138,7 @@ SIGNATURES = {
 }
 
 COMM_ID_BYTES = 128
+SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*
 
 _lib = None

@@ -25,6 +25,7 @@ import torch
 
 from . import dist, ops
 from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_LRELU
+from .layers import SpectralNormalization
 
 
 RESAMPLE = ("upsample", "avgpool")
@@ -295,6 +296,16 @@ class Net:
             raise NotImplementedError("UpSampling2D / AveragePooling2D must stand between two linear layers, not first or last in a network")
         self.out_shape = self.stages[-1].out_shape
         self.conv_layers = [st.lin for st in self.stages if st.kind in ("conv", "convT")]
+        # layers.SpectralNormalization: the engine reads W / sigma (and its transposed copy) of these from the store's effective-weight
+        # buffer, which spectral_update() fills; the plain conv layers keep their batched transpose
+        self.spectral_layers = [st.lin for st in self.stages if isinstance(st.lin, SpectralNormalization)]
+        self.plain_conv_layers = [l for l in self.conv_layers if not isinstance(l, SpectralNormalization)]
+        # power rounds per optimizer step, read ONCE here (0: no wrapped layer): part of the step-program key; changing a layer's
+        # power_iterations on a built model has no effect
+        rounds = {l.power_iterations for l in self.spectral_layers}
+        if len(rounds) > 1:
+            raise NotImplementedError(f"SpectralNormalization layers of one model must share power_iterations, got {sorted(rounds)}")
+        self.spectral_rounds = rounds.pop() if rounds else 0
         self.has_ln = any(st.ln is not None for st in self.stages)
         self._ctx = {}
         self._ws = None
@@ -338,9 +349,9 @@ class Net:
         lin = st.lin
         epi = self._epi(bwd_data, x.size(0), *st.geom, mode, **kw)
         if bwd_data:
-            ops.conv2d_bwd_data(x, lin.vars["kernel"], y, lin.k, lin.stride, epi, math=self.conv_math)
+            ops.conv2d_bwd_data(x, self.store.kernel(lin), y, lin.k, lin.stride, epi, math=self.conv_math)
         else:
-            ops.conv2d_fwd(x, self.store.transposed_kernel(lin), y, lin.k, lin.stride, epi, math=self.conv_math)
+            ops.conv2d_fwd(x, self.store.kernel(lin, transposed=True), y, lin.k, lin.stride, epi, math=self.conv_math)
         return epi
 
     def _filter_grad(self, st, a, dz, beta, scale):
@@ -352,8 +363,30 @@ class Net:
         ops.conv2d_bwd_filter(x, dy, dW, st.lin.k, st.lin.stride, beta, scale, self.workspace(nb) if nb else None)
 
     def prepare_weights(self):
-        """(Re)builds the transposed kernel copies the 'other direction' of each conv needs."""
-        self.store.refresh_transposed(self.conv_layers)
+        """(Re)builds what the passes read in place of changed weights: W / sigma of the spectrally normalised layers (sigma = v^T W u
+        refreshed, no power round) and the transposed kernel copies the 'other direction' of each conv needs."""
+        self.spectral_update(iterate=False)
+        self.store.refresh_transposed(self.plain_conv_layers)
+
+    # ---- spectral normalisation (DESIGN.md §5 "Spectral normalisation").  Public names, as the LayerNormalization helpers below:
+    # the engine-trace fixture's configurations have no such layer; tests/test_spectral_cpu.py records what these enqueue.
+    def spectral_update(self, iterate=True):
+        """The wrapped layers' sigma and effective weights.  ``iterate``: the layers' power rounds (the start of this model's optimizer
+        step), else sigma = v^T W u with the stored vectors, and only if the weights changed since the last update.  Then W / sigma
+        with its transposed copies, one launch for all layers."""
+        if not self.spectral_layers or not (iterate or self.store.sn_dirty):
+            return
+        table = self.store.spectral_table(self.spectral_layers)
+        for _ in range(self.spectral_rounds if iterate else 1):
+            ops.spectral.power(self.store.theta, self.store.state, table, sigma_only=not iterate)
+        ops.spectral.scale(self.store.theta, self.store.state, self.store.eff, table)
+        self.store.sn_dirty = False
+
+    def spectral_project_gradients(self):
+        """store.grad holds dL/dW-bar of the wrapped layers (the passes ran on W-bar = W / sigma): in place, dL/dW =
+        (g - <g, W-bar> v u^T) / sigma, u and v held constant.  Linear, with u, v, sigma equal on all ranks: after the all-reduce."""
+        if self.spectral_layers:
+            ops.spectral.grad(self.store.grad, self.store.eff, self.store.state, self.store.spectral_table(self.spectral_layers))
 
     def blur_taps(self, H, W):
         """(device buffer, tap count) of the layer's CURRENT std for H x W images (gaussian_blur.py:21-31,83-88 through
@@ -488,7 +521,7 @@ class Net:
         tgt = ctx.z[i] if st.bn is not None else out
         stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
         if st.kind == "dense":
-            ops.gemm(xin, st.lin.vars["kernel"], tgt, ctx.B, st.out_shape[0], st.in_shape[0], bias=bias)
+            ops.gemm(xin, self.store.kernel(st.lin), tgt, ctx.B, st.out_shape[0], st.in_shape[0], bias=bias)
         elif st.folds_inference_bn and not training:
             scale, shift = self._fold_out(ctx, i)
             if not folded:
@@ -730,7 +763,7 @@ class Net:
                 lo, hi = dx_rows
                 dz, tgt = dz.view(ctx.B, *st.out_shape)[lo:hi], tgt[lo:hi]
             if st.kind == "dense":
-                ops.gemm(dz, st.lin.vars["kernel"], tgt, tgt.size(0), st.in_shape[0], st.out_shape[0], transB=True)
+                ops.gemm(dz, self.store.kernel(st.lin), tgt, tgt.size(0), st.in_shape[0], st.out_shape[0], transB=True)
             elif fuse:
                 keep, scale, keep_elems = ctx.dropout(i - 1)
                 self._conv(st, dz, tgt, True, EPI_MUL_GRAD, ref=ctx.a[i - 1], keep=keep, alpha=prev.alpha, scale=scale, keep_elems=keep_elems)

@@ -171,6 +171,62 @@ class LayerNormalization(Layer):
         return [("gamma", (c,), True, _ones((c,))), ("beta", (c,), True, _zeros((c,)))]
 
 
+def _normalize(x):
+    """x / max(||x||, 1e-12): the normalisation of the power iteration."""
+    return x / max(float(np.linalg.norm(x)), 1e-12)
+
+
+class SpectralNormalization(Layer):
+    """tf.keras.layers.SpectralNormalization(layer, power_iterations=1) around a Conv2D, Conv2DTranspose or Dense (Miyato et al.
+    2018).  The layer's kernel, viewed as the matrix W = reshape(kernel, [-1, shape[-1]]), is divided by sigma, its largest singular
+    value as a running power iteration estimates it; ``vector_u``, ``vector_v`` and ``sigma`` are non-trainable state behind the
+    layer's own variables.  In a Sequential the wrapper stands for the layer it wraps: same kind, shapes, variables and fusion.
+    One power round runs per optimizer step of the model, at the start of that step; every other use of changed weights refreshes
+    sigma = v^T W u alone (DESIGN.md section 5 "Spectral normalisation")."""
+
+    def __init__(self, layer, power_iterations=1, **kw):
+        if not isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
+            raise NotImplementedError(f"SpectralNormalization wraps a Conv2D, a Conv2DTranspose or a Dense, not {type(layer).__name__}")
+        if int(power_iterations) < 1:
+            raise ValueError(f"power_iterations={power_iterations!r}: at least one power round per step")
+        kw.setdefault("input_shape", layer._declared_input_shape)
+        kw.setdefault("name", "spectral_normalization_" + layer.name)
+        super().__init__(**kw)
+        self.layer, self.power_iterations = layer, int(power_iterations)
+        self.kind = layer.kind
+        layer.vars = self.vars      # one set of variables, reachable through either object
+
+    def __getattr__(self, name):    # what the wrapper does not have itself (filters, k, stride, units, activation, ...) is the layer's
+        if name == "layer" or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.layer, name)
+
+    def out_shape(self, in_shape):
+        return self.layer.out_shape(in_shape)
+
+    @staticmethod
+    def matrix_shape(kernel_shape):
+        """(K, N, taps) of a kernel variable: the row-major matrix [K, N] = reshape(kernel, [-1, shape[-1]]), K = taps * R."""
+        n = int(kernel_shape[-1])
+        k = int(np.prod(kernel_shape)) // n
+        return k, n, (int(kernel_shape[0]) * int(kernel_shape[1]) if len(kernel_shape) == 4 else 1)
+
+    def var_specs(self, in_shape):
+        specs = list(self.layer.var_specs(in_shape))
+        K, N, _ = self.matrix_shape(specs[0][1])
+        u0 = lambda rng: _normalize(rng.normal(0.0, 0.02, (N,))).astype(np.float32)
+        # vector_v and sigma follow from W and u0: ParamStore sets them once the kernel has its initial value
+        return specs + [("vector_u", (N,), False, u0), ("vector_v", (K,), False, _zeros((K,))), ("sigma", (1,), False, _ones((1,)))]
+
+    def init_state(self):
+        """v0 = normalize(W u0), sigma = v0^T W u0 from the initial kernel and u0, on the host."""
+        W = self.vars["kernel"].detach().cpu().numpy().astype(np.float64).reshape(-1, self.vars["kernel"].shape[-1])
+        u = self.vars["vector_u"].detach().cpu().numpy().astype(np.float64)
+        v = _normalize(W @ u)
+        self.vars["vector_v"].copy_(torch.from_numpy(v.astype(np.float32)))
+        self.vars["sigma"].copy_(torch.from_numpy(np.array([v @ W @ u], dtype=np.float32)))
+
+
 class LeakyReLU(Layer):
     kind = "lrelu"
 
@@ -264,7 +320,7 @@ class ParamStore:
         self.device = torch.device(device)
         self.entries = []       # (layer, name, offset, shape, trainable)
         off_t = off_s = 0
-        init_vals = []
+        init_vals, fresh_spectral = [], []
         for layer, in_shape in layers_with_shapes:
             for name, shape, trainable, init in layer.var_specs(in_shape):
                 n = int(np.prod(shape))
@@ -277,6 +333,8 @@ class ParamStore:
                     self.entries.append((layer, name, off_s, tuple(shape), False))
                     off_s += -(-n // self.ALIGN) * self.ALIGN
                 init_vals.append(val)
+                if name == "vector_v" and old is None:
+                    fresh_spectral.append(layer)
         self.n_train, self.n_state = off_t, off_s
         self.theta = torch.zeros(max(off_t, 1), dtype=torch.float32, device=self.device)
         self.state = torch.zeros(max(off_s, 1), dtype=torch.float32, device=self.device)
@@ -292,7 +350,23 @@ class ParamStore:
             layer.vars[name] = view
         # transposed copies of conv kernels ([taps][C][R] from [taps][R][C]) for the direction that needs them
         self._tr = {}           # id(layer) -> tensor
+        # spectrally normalised layers: the engine reads W / sigma and its transposed copy from one flat effective-weight buffer,
+        # laid out with the descriptor table by spectral_table(); without such layers nothing is allocated
+        self.eff = None
+        self._sn = {}           # id(layer) -> (effective kernel view, transposed view or None)
+        self._sn_table = None
+        for layer in fresh_spectral:
+            layer.init_state()
         self.tr_dirty = True
+
+    @property
+    def tr_dirty(self):
+        """The weights changed since the copies derived from them (transposed kernels, W / sigma) were made."""
+        return self._tr_dirty
+
+    @tr_dirty.setter
+    def tr_dirty(self, value):
+        self._tr_dirty = self.sn_dirty = bool(value)        # sn_dirty alone is cleared by the step's own power round
 
     def ensure_opt_state(self):
         if self.grad is None:
@@ -332,6 +406,46 @@ class ParamStore:
     def grad_of(self, layer, name):
         self.ensure_opt_state()
         return self.view_like(self.grad, layer, name)
+
+    def kernel(self, layer, transposed=False):
+        """The kernel the engine computes with: the layer's own variable (``transposed``: its [k*k][C][R] copy), or for a spectrally
+        normalised layer W / sigma and its transposed copy in the effective-weight buffer."""
+        if isinstance(layer, SpectralNormalization):
+            views = self._sn.get(id(layer))
+            if views is None:
+                raise KeyError("effective weights are laid out by spectral_table(); call Net.prepare_weights() first")
+            return views[1 if transposed else 0]
+        return self.transposed_kernel(layer) if transposed else layer.vars["kernel"]
+
+    def _state_offset(self, layer, name):
+        return next(off for (l, n, off, _, tr) in self.entries if l is layer and n == name and not tr)
+
+    def spectral_table(self, layers):
+        """The descriptor table (ops.SpectralTable) of the spectrally normalised ``layers`` and, with it, the effective-weight buffer:
+        per layer W / sigma [K, N] and, for conv kinds, the transposed copy the other direction of the conv reads."""
+        key = [id(l) for l in layers]
+        if self._sn_table is not None and self._sn_table[0] == key:
+            return self._sn_table[1]
+        from . import ops
+        pad = lambda n: -(-n // self.ALIGN) * self.ALIGN
+        rows, views, off = [], {}, 0
+        for layer in layers:
+            w = layer.vars["kernel"]
+            K, N, taps = SpectralNormalization.matrix_shape(w.shape)
+            w_off = (w.data_ptr() - self.theta.data_ptr()) // 4
+            assert 0 <= w_off < self.theta.numel() and w_off % 4 == 0
+            eff_off, off = off, off + pad(K * N)
+            tr_off = -1
+            if layer.kind in ("conv", "convT"):
+                tr_off, off = off, off + pad(K * N)
+            rows.append(dict(w_off=w_off, u_off=self._state_offset(layer, "vector_u"), v_off=self._state_offset(layer, "vector_v"),
+                             sigma_off=self._state_offset(layer, "sigma"), eff_off=eff_off, tr_off=tr_off, K=K, N=N, taps=taps))
+            views[id(layer)] = (eff_off, tr_off, K * N, tuple(w.shape))
+        self.eff = torch.empty(max(off, 4), dtype=torch.float32, device=self.device)
+        self._sn = {k: (self.eff[e:e + n].view(shape), None if t < 0 else self.eff[t:t + n]) for k, (e, t, n, shape) in views.items()}
+        table = ops.SpectralTable(ops.spectral.rows(rows), self.device)
+        self._sn_table = (key, table)
+        return table
 
     def transposed_kernel(self, layer):
         """[k*k][C][R] copy of a conv kernel stored [k*k][R][C]; refreshed after every optimiser step."""
@@ -510,3 +624,14 @@ class Sequential(Layer):
     def __call__(self, x, training=False):
         """Forward pass on the HIP kernels; returns a fresh tensor [B, *output_shape]."""
         return self.net().predict(x, training=training)
+
+
+class SpectralSequential(Sequential):
+    """A Sequential that, with its ``spectral_norm`` attribute set, wraps every Conv2D, Conv2DTranspose and Dense added to it into a
+    SpectralNormalization (the DCGAN stacks' ``spectral_norm=`` argument)."""
+    spectral_norm = False
+
+    def add(self, layer):
+        if self.spectral_norm and isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
+            layer = SpectralNormalization(layer)
+        super().add(layer)

@@ -13,7 +13,10 @@ stage convolves at the higher resolution: 4x the multiply-adds of the strided la
 
 The critic takes ``normalization="layer"``: a LayerNormalization over the channels between every Conv2D and its LeakyReLU (the
 WGAN-GP paper's critic; BatchNormalization cannot stand there, the penalty is defined per sample).  Map sizes are unchanged, every
-block gains 2 * C variables; it combines with ``downsampling="pool"``."""
+block gains 2 * C variables; it combines with ``downsampling="pool"``.
+
+``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
+engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``."""
 from __future__ import annotations
 
 from . import layers
@@ -34,9 +37,10 @@ IMAGE_SHAPE = {"mnist": (28, 28, 1), "celeba128": (128, 128, 3), "celeba64": (64
 LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mnist": 6, "tiny_k3": 10}
 
 
-class DCGANGenerator(layers.Sequential):
-    def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", **kwargs):
+class DCGANGenerator(layers.SpectralSequential):
+    def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         if upsampling not in ("transpose", "resize"):
             raise ValueError(f"upsampling must be 'transpose' or 'resize', got {upsampling!r}")
         self.upsampling = upsampling
@@ -65,9 +69,10 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None,) + IMAGE_SHAPE[arch], self.output_shape
 
 
-class DCGANDiscriminator(layers.Sequential):
-    def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, **kwargs):
+class DCGANDiscriminator(layers.SpectralSequential):
+    def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         if downsampling not in ("stride", "pool"):
             raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
         if normalization not in (None, "layer"):

@@ -417,6 +417,76 @@ class layernorm:
         return s
 
 
+# ------------------------------------------------------------------ spectral normalisation (include/bgan.h "spectral normalisation")
+class SpectralTable:
+    """The descriptor table of one batch of wrapped layers: the rows in host memory (the calls check them before anything touches
+    the device), their device copy (the kernels read it) and the workspace the table asks for."""
+
+    def __init__(self, rows, device):
+        import numpy as np
+        self.host = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, _lib.SPECTRAL_DESC_INTS)
+        self.n = int(self.host.shape[0])
+        self.dev = torch.from_numpy(self.host.copy()).to(device)
+        self.ws_bytes = spectral.workspace_bytes(self.host)
+        self.ws = torch.empty(max(self.ws_bytes // 4, 4), dtype=torch.float32, device=device)
+
+
+class spectral:
+    """The SpectralNormalization kernels, batched over a SpectralTable.  A namespace for the reason ``layernorm`` is one: the
+    engine-trace maker refuses module-level functions it does not know."""
+
+    @staticmethod
+    def route(K, N, taps=1):
+        """How the kernels cut a [K, N] matrix: dict(vec, lanes, chunks, strip_rows, pass_units, ew_units, tiles, ws_floats)."""
+        names = ("vec", "lanes", "chunks", "strip_rows", "pass_units", "ew_units", "tiles", "ws_floats")
+        v = [C.c_int() for _ in names]
+        check(_lib.load().bg_spectral_route(int(K), int(N), int(taps), *[C.byref(x) for x in v]), "bg_spectral_route")
+        return {k: x.value for k, x in zip(names, v)}
+
+    @staticmethod
+    def rows(layers):
+        """Table rows for ``layers`` = [dict(w_off, u_off, v_off, sigma_off, eff_off, tr_off, K, N, taps)]: the first units and the
+        workspace offsets are running sums of what ``route`` gives."""
+        out, pf, ef, tf, ws = [], 0, 0, 0, 0
+        for l in layers:
+            r = spectral.route(l["K"], l["N"], l["taps"])
+            out.append([l["w_off"], l["u_off"], l["v_off"], l["sigma_off"], l["eff_off"], l["tr_off"], l["K"], l["N"], l["taps"], pf, ef, tf, ws, 0, 0, 0])
+            pf, ef, tf, ws = pf + r["pass_units"], ef + r["ew_units"], tf + r["tiles"], ws + r["ws_floats"]
+        return out
+
+    @staticmethod
+    def _host(rows):
+        assert rows.dtype.name == "int32" and rows.flags["C_CONTIGUOUS"] and rows.shape[1] == _lib.SPECTRAL_DESC_INTS
+        return rows.ctypes.data, int(rows.shape[0])
+
+    @staticmethod
+    def workspace_bytes(host_rows):
+        return _lib.load().bg_spectral_workspace_bytes(*spectral._host(host_rows))
+
+    @staticmethod
+    def power(theta, state, table, sigma_only=False):
+        """One power round over every layer of ``table`` (u, v, sigma in ``state``), or sigma = v^T W u alone."""
+        _f32(theta, state)
+        check(_lib.load().bg_spectral_power_f32(_ptr(theta), _ptr(state), _ptr(table.dev), *spectral._host(table.host), int(bool(sigma_only)),
+                                                _ptr(table.ws), table.ws.numel() * 4, _stream()), "bg_spectral_power_f32")
+
+    @staticmethod
+    def scale(theta, state, eff, table):
+        """eff = W / sigma, with the transposed copies of the conv kernels."""
+        _f32(theta, state, eff)
+        check(_lib.load().bg_spectral_scale_f32(_ptr(theta), _ptr(state), _ptr(eff), _ptr(table.dev), *spectral._host(table.host), _stream()),
+              "bg_spectral_scale_f32")
+        return eff
+
+    @staticmethod
+    def grad(grad, eff, state, table):
+        """In place on the flat gradient buffer: dL/dW-bar -> dL/dW = (g - <g, W-bar> v u^T) / sigma."""
+        _f32(grad, eff, state)
+        check(_lib.load().bg_spectral_grad_f32(_ptr(grad), _ptr(eff), _ptr(state), _ptr(table.dev), *spectral._host(table.host), _ptr(table.ws),
+                                               table.ws.numel() * 4, _stream()), "bg_spectral_grad_f32")
+        return grad
+
+
 # ------------------------------------------------------------------ pointwise / losses / optimisers / rng
 def lerp(r, f, alpha_b, out):
     B = r.shape[0]

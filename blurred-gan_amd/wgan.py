@@ -125,6 +125,9 @@ class WGAN:
         # Keras optimizer objects (optimizers.py); any supported one may be assigned to either network at any time
         self.generator = generator
         self.generator.build()
+        if ema_schedule is not None and self.generator.net().spectral_layers:
+            raise NotImplementedError("generator_ema with a spectrally normalised generator: an averaged vector_u is no unit vector, and "
+                                      "the averaged model would need a power iteration of its own")
         self.generator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.discriminator = discriminator
         self.discriminator.build()
@@ -321,6 +324,9 @@ class WGAN:
                self.merge_gp_filter_gradients, self.sync_batchnorm, self.gp_zero_norm_guard, self.reproduce_vector_loss_quirk,
                self.sync_metrics, dist.collectives_active(), dist.world_size(), G.fuse_bn_stats, D.fuse_bn_stats,
                G.store.n_train, D.store.n_train, G.conv_math, D.conv_math, _env_switches(), hp,
+               # spectral normalisation: the rounds per step, and whether the effective weights are stale on their own (a round taken by
+               # hand between two steps clears sn_dirty and leaves tr_dirty: the step then skips a refresh a recorded program holds)
+               G.spectral_rounds, D.spectral_rounds, G.store.sn_dirty, D.store.sn_dirty,
                self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
         if self.generator_ema is not None:
             # the averaged model's presence, the two buffers the update writes and the schedule's static configuration: a program
@@ -407,6 +413,7 @@ class WGAN:
         self.batch_size = B
         hp = self.hparams
         G, D = self.generator.net(), self.discriminator.net()
+        D.spectral_update()         # a spectrally normalised critic: its power round, before any forward of this step
         z = self._inj("z_d")
         z = self._as_device(z) if z is not None else self._uniform("z_d", (B, self.latent_size))
         fakes = G.forward(G.context(B, "g_dstep"), z, training=False)           # Q4: inference BN in the D-step
@@ -467,6 +474,7 @@ class WGAN:
             if self.uses_gradient_penalty:
                 D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms), reducer=red)
         red.finish()
+        D.spectral_project_gradients()
         optimizers.get_optimizer(self.discriminator).apply(store)
         disc_loss = None              # inside train_on_batch the value is read with the rest of the step's metrics
         if self.sync_metrics and not self._defer_metrics:
@@ -519,6 +527,7 @@ class WGAN:
         """wgan.py:159-172."""
         B = self.batch_size
         G, D = self.generator.net(), self.discriminator.net()
+        G.spectral_update()         # a spectrally normalised generator: its power round
         z = self._inj("z_g")
         z = self._as_device(z) if z is not None else self._uniform("z_g", (B, self.latent_size))
         cg = G.context(B, "g")
@@ -535,6 +544,7 @@ class WGAN:
         red = dist.GradReducer(store.grad, store.n_train)
         G.backward(cg, dfakes, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=red)
         red.finish()
+        G.spectral_project_gradients()
         optimizers.get_optimizer(self.generator).apply(store)
         if self.generator_ema is not None:
             self._update_generator_ema()

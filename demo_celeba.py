@@ -26,11 +26,12 @@ def make_dataset(batch_size, n_batches=None, seed=0):
     return [torch.from_numpy(rng.uniform(-1, 1, size=(batch_size, 128, 128, 3)).astype(np.float32)) for _ in range(n_batches or 16)]
 
 
-class DCGANGenerator(layers.Sequential):
+class DCGANGenerator(layers.SpectralSequential):
     """demo_celeba.py:51-93."""
 
-    def __init__(self, latent_size=100, *args, upsampling="transpose", **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         self.latent_size = latent_size
         resize = {"transpose": False, "resize": True}[upsampling]
         self.add(layers.Dense(4 * 4 * 512, use_bias=False, input_shape=(self.latent_size,)))
@@ -53,11 +54,12 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, 128, 128, 3), self.output_shape
 
 
-class DCGANDiscriminator(layers.Sequential):
+class DCGANDiscriminator(layers.SpectralSequential):
     """demo_celeba.py:96-124."""
 
-    def __init__(self, *args, downsampling="stride", normalization="none", **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         pool = {"stride": False, "pool": True}[downsampling]
         norm = {"none": False, "layer": True}[normalization]
         for i, c in enumerate((16, 32, 64, 128, 256, 512)):
@@ -92,6 +94,12 @@ def make_parser():
     parser.add_argument("--critic-norm", dest="critic_norm", default="none", choices=["none", "layer"],
                         help="critic normalisation: none (default, the reference's) or a LayerNormalization over the channels between "
                              "every Conv2D and its LeakyReLU (the WGAN-GP paper's critic)")
+    parser.add_argument("--critic-spectral-norm", dest="critic_spectral_norm", action="store_true",
+                        help="spectral normalisation (Miyato et al. 2018) of every Conv2D and Dense of the critic: the step computes "
+                             "with W / sigma, one power round per critic step")
+    parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
+                        help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
+                             "the generator average)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -131,7 +139,8 @@ def main(argv=None):
         total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
-    gen, disc = DCGANGenerator(upsampling=args.upsampling), DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm)
+    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm)
+    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

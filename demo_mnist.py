@@ -28,11 +28,12 @@ def make_dataset(batch_size, n_batches=None, shuffle_buffer_size=256, seed=0):
     return [torch.from_numpy(x[idx[i:i + batch_size]]) for i in range(0, len(x) - batch_size + 1, batch_size)][:n_batches]
 
 
-class DCGANGenerator(layers.Sequential):
+class DCGANGenerator(layers.SpectralSequential):
     """demo_mnist.py:48-71."""
 
-    def __init__(self, latent_size=100, *args, upsampling="transpose", **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         self.latent_size = latent_size
         resize = {"transpose": False, "resize": True}[upsampling]
 
@@ -59,11 +60,12 @@ class DCGANGenerator(layers.Sequential):
         assert self.output_shape == (None, 28, 28, 1)
 
 
-class DCGANDiscriminator(layers.Sequential):
+class DCGANDiscriminator(layers.SpectralSequential):
     """demo_mnist.py:74-86."""
 
-    def __init__(self, *args, downsampling="stride", normalization="none", **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, **kwargs):
         super().__init__(*args, **kwargs)
+        self.spectral_norm = bool(spectral_norm)
         pool = {"stride": False, "pool": True}[downsampling]
         norm = {"none": False, "layer": True}[normalization]
         strides = (1, 1) if pool else (2, 2)
@@ -104,6 +106,12 @@ def make_parser():
     parser.add_argument("--critic-norm", dest="critic_norm", default="none", choices=["none", "layer"],
                         help="critic normalisation: none (default, the reference's) or a LayerNormalization over the channels between "
                              "every Conv2D and its LeakyReLU (the WGAN-GP paper's critic)")
+    parser.add_argument("--critic-spectral-norm", dest="critic_spectral_norm", action="store_true",
+                        help="spectral normalisation (Miyato et al. 2018) of every Conv2D and Dense of the critic: the step computes "
+                             "with W / sigma, one power round per critic step")
+    parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
+                        help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
+                             "the generator average)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -150,8 +158,8 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "mnist") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
-    gen = DCGANGenerator(upsampling=args.upsampling)
-    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm)
+    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm)
+    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

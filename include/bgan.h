@@ -289,6 +289,41 @@ int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int
 int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float* s, int R, int C, const float* gamma, const float* mu,
                         const float* r, float* dgamma, float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- spectral normalisation (Miyato et al. 2018; layers.SpectralNormalization) -------------------------------------------
+ * A wrapped layer's kernel is the row-major matrix W[K, N] (N = the kernel's last axis, K = the rest); the engine runs on
+ * W-bar = W / sigma, sigma from a running power iteration with the unit vectors u[N], v[K] (layer state).
+ *
+ * Every call is batched over all wrapped layers of one model.  The table has BG_SPECTRAL_DESC_INTS int32 per layer:
+ *   {w_off, u_off, v_off, sigma_off, eff_off, tr_off, K, N, taps, pass_first, ew_first, tile_first, ws_off, 0, 0, 0}
+ * w_off: floats from `theta` (and from the flat gradient buffer); u_off / v_off / sigma_off: from `state`; eff_off / tr_off: from
+ * the effective-weight base (tr_off = -1: no transposed copy); ws_off: from the workspace.  All but sigma_off are multiples of 4.
+ * taps divides K (k * k for conv kernels, 1 for Dense).  pass_first / ew_first / tile_first: the layer's first work unit in the
+ * power pass, in the dot / apply kernels and in the scale kernel -- running sums of bg_spectral_route's pass_units / ew_units /
+ * tiles.  The table is handed over twice: desc_d on the device, which the kernels read, and the same rows in host memory, desc_h,
+ * which the call checks before anything touches the device: null pointer BG_ERR_NULL, K / N / taps <= 0 or first units that do not
+ * continue the table BG_ERR_BAD_SHAPE, a base or an offset that is not 16-byte aligned BG_ERR_BAD_ALIGNMENT, a workspace smaller
+ * than bg_spectral_workspace_bytes BG_ERR_WORKSPACE.  A matrix is cut into units by (K, N, taps) alone, partial sums are added in
+ * unit order and nothing is atomic: results are the same bits from run to run and for any batching of the layers. */
+#define BG_SPECTRAL_DESC_INTS 16
+/* pure host query: how [K, N] is laid over a wave (vec floats per access, `lanes` lanes per row, `chunks` vectors per lane; chunks
+ * = 0: rows wider than a wave holds, a wave strides over its row), the rows of a pass unit, the unit counts, the workspace floats */
+int bg_spectral_route(int K, int N, int taps, int* vec, int* lanes, int* chunks, int* strip_rows, int* pass_units, int* ew_units,
+                      int* tiles, int* ws_floats);
+/* pure host query over a host table; 0 for a table the calls would refuse */
+size_t bg_spectral_workspace_bytes(const int* desc_h, int n);
+/* One power round: t = W u, v = t / max(||t||, 1e-12), s = W^T v, u = s / max(||s||, 1e-12), sigma = s . u (= v^T W u) -- W is
+ * read once: a workgroup takes a strip of rows and adds t_r * W[r, :] while row r is in registers; a second launch adds the
+ * strips' partials.  sigma_only != 0: sigma = v^T W u with the stored u and v, both left as they are. */
+int bg_spectral_power_f32(const float* theta, float* state, const int* desc_d, const int* desc_h, int n, int sigma_only, float* ws_d,
+                          size_t ws_bytes, void* stream);
+/* eff[eff_off + i] = W[i] / sigma, and where tr_off >= 0 the copy eff[tr_off + (t * N + c) * R + r] of element (t * R + r, c), R =
+ * K / taps: the [taps][C][R] array bg_conv2d_fwd reads, out of the same launch (no bg_transpose_last2_batched for such a model) */
+int bg_spectral_scale_f32(const float* theta, const float* state, float* eff, const int* desc_d, const int* desc_h, int n, void* stream);
+/* g = dL/dW-bar in the flat gradient buffer (at w_off) becomes dL/dW, u and v held constant:
+ *   g <- (g - <g, W-bar> * v u^T) / sigma         (two launches: the dot's per-workgroup partials, then the apply) */
+int bg_spectral_grad_f32(float* grad, const float* eff, const float* state, const int* desc_d, const int* desc_h, int n, float* ws_d,
+                         size_t ws_bytes, void* stream);
+
 /* ---- pointwise ------------------------------------------------------------------------------ */
 /* wgan.py:239: xhat[b,:] = r[b,:] + alpha[b] * (f[b,:] - r[b,:]) */
 int bg_lerp_f32(const float* r, const float* f, const float* alpha_b, float* xhat, int B, int n_per, void* stream);
