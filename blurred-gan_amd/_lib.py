@@ -79,7 +79,11 @@ SIGNATURES = {
     "bg_ln_bwd_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _f, _z, _p, _p, _i, _i, _p, _p, _i, _f, _f, _p, _z, _p]),
     "bg_ln_tangent_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p]),
     "bg_ln_gp_source_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _f, _p, _z, _p]),
-    "bg_spectral_route": (_i, [_i, _i, _i] + [C.POINTER(_i)] * 8),
+    "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
+    "bg_diffaug_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
+    "bg_diffaug_adjoint_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "bg_spectral_route":(_i, [_i, _i, _i] + [C.POINTER(_i)] * 8),
     "bg_spectral_workspace_bytes": (_z, [_p, _i]),
     "bg_spectral_power_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _z, _p]),
     "bg_spectral_scale_f32": (_i, [_p, _p, _p, _p, _p, _i, _p]),

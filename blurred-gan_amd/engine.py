@@ -124,6 +124,7 @@ class Context(_StageBuffers):
         self._extra = {}
         self._bn_grad_scratch = {}
         self.dropout_active = False
+        self.aug = None             # (DiffAugment, params [B, 8]) of this pass's last forward: what its backward applies L^T with
 
     def keep_elems(self, i):
         """Output elements of stage i covered by its dropout mask (0 = all of them): the bg_epilogue.keep_elems field."""
@@ -179,6 +180,12 @@ class Context(_StageBuffers):
             self.u[i] = torch.empty((n,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
         self.u_rows = tuple(rows)
         return self.u[i]
+
+    def aug_input(self):
+        """The augmented input batch T(blur(x)): stage 0's input of a pass with DiffAugment, next to the (blurred) batch in a0."""
+        if "aug_input" not in self._extra:
+            self._extra["aug_input"] = torch.empty_like(self.a0)
+        return self._extra["aug_input"]
 
     def blur_grad(self):
         """Where blur^T of the input gradient goes when the blurred input itself has to survive the backward."""
@@ -440,15 +447,19 @@ class Net:
             return ops.blur_nhwc(x, y, taps, nt, tmp)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, ctx: Context, inputs, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None):
+    def forward(self, ctx: Context, inputs, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None, augment=None):
         """inputs: a tensor [B,...] or a list of tensors concatenated along the batch.  ``training`` switches
         Dropout and BatchNormalization exactly as Keras' ``training=`` argument does.
         ``lerp_alpha`` (with inputs = [f, r]): a third batch slice x-hat = r + alpha (f - r) follows the two (wgan.py:239).  Behind
         a blur layer of a geometry the row-block kernel takes, all three slices are blurred by ONE launch that forms x-hat on the
-        fly (bg_blur3_lerp_nhwc_f32); otherwise x-hat is written to ``lerp_out`` by bg_lerp_f32 and joins the list."""
+        fly (bg_blur3_lerp_nhwc_f32); otherwise x-hat is written to ``lerp_out`` by bg_lerp_f32 and joins the list.
+        ``augment`` = (DiffAugment, params [B, 8]): the assembled (blurred) batch goes through T into a second input-sized buffer,
+        which is what stage 0 reads; the pass's backward applies L^T ahead of blur^T (aug_forward / aug_backward)."""
         if self.store.tr_dirty:
             self.prepare_weights()
         x = self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)
+        ctx.aug = augment
+        if augment is not None: x = self.aug_forward(ctx, x)      # noqa: E701
         ctx.dropout_active = bool(training)
         # one launch draws the masks of all stages; where their rates differ, or masks are handed in, each stage sets its own
         one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
@@ -640,6 +651,7 @@ class Net:
                 p.release_deferred()        # slices finished before this exchange was issued may go out behind it now
                 self._weight_grads(p, i, st, dz, defer_ready=True)
         p.release_deferred()
+        if ctx.aug is not None: return self.aug_backward(ctx, g, dx_rows)      # noqa: E701
         if self.blur is not None:
             # forward's blurred input is dead by now; reuse it for blur^T(din) -- unless the penalty's LayerNormalization source
             # backward follows (keep_u_rows): its first filter gradient reads the blurred x-hat
@@ -770,6 +782,30 @@ class Net:
             else:
                 self._conv(st, dz, tgt, True, EPI_NONE)
         return tgt, fuse
+
+    # ---- DiffAugment in front of stage 0 (DESIGN.md §5 "Augmentation").  Public names for the reason the LayerNormalization helpers
+    # carry them: the engine-trace fixture's configurations run without augmentation; tests/test_diffaug_cpu.py records these.
+    def aug_forward(self, ctx, x):
+        """ctx.aug_input() = T(x) for the pass's (blurred) input batch ``x``: always a copy, with or without blur."""
+        cfg, params = ctx.aug
+        assert len(self.in_shape) == 3, "DiffAugment needs an [H, W, C] network input"
+        assert tuple(params.shape) == (ctx.B, 8), f"augmentation params {tuple(params.shape)} for a pass of {ctx.B} samples"
+        return ops.diffaug.fwd(x.view(ctx.B, *self.in_shape), ctx.aug_input(), params, **cfg.kernel_args())
+
+    def aug_linear(self, cfg, params, v, out):
+        """out = L v: the linear part of T for the rows ``params`` belongs to (the penalty's second-order seed)."""
+        return ops.diffaug.fwd(v.view(-1, *self.in_shape), out.view(-1, *self.in_shape), params, **cfg.kernel_args(), linear=True)
+
+    def aug_backward(self, ctx, g, dx_rows):
+        """The end of a backward whose forward was augmented: L^T of the stage-0 input gradient ``g`` (all rows, or ``dx_rows``),
+        then blur^T.  Stage 0 read ctx.aug_input(), so the blurred batch in ctx.a0 has been dead since the forward: L^T lands in
+        its rows, and blur^T goes back into the rows of the input-gradient buffer ``g`` came in.  The augmented batch itself is
+        left alone: the layer-1 filter gradients of the penalty (merged, or the LayerNormalization source backward) still read it."""
+        cfg, params = ctx.aug
+        lo, hi = (0, ctx.B) if dx_rows is None else dx_rows
+        g = g.view(hi - lo, *self.in_shape)
+        dx = ops.diffaug.adjoint(g, ctx.a0[lo:hi], params[lo:hi], **cfg.kernel_args())
+        return dx if self.blur is None else self.apply_blur(dx, g)
 
     # ------------------------------------------------------------------ GP second order
     def _gp_kinds(self):

@@ -417,6 +417,49 @@ class layernorm:
         return s
 
 
+# ------------------------------------------------------------------ differentiable augmentation (include/bgan.h)
+class diffaug:
+    """The DiffAugment kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's public
+    functions by name; these calls are recorded by the augmentation tests' own recorder."""
+
+    @staticmethod
+    def route(H, W, Cc):
+        """dict(resident, resident_floats): whether a sample of this geometry waits in LDS between its mean and its use."""
+        r, f = C.c_int(), C.c_int()
+        check(_lib.load().bg_diffaug_route(int(H), int(W), int(Cc), C.byref(r), C.byref(f)), "bg_diffaug_route")
+        return dict(resident=bool(r.value), resident_floats=f.value)
+
+    @staticmethod
+    def decode(u, H, W, ops_mask=7, translation_ratio=0.125, cutout_ratio=0.5):
+        """The library's own decode of one row of eight uniforms, on the host: dict(b, s, c, ty, tx, y0, x0, cy, cx, Sy, Sx)."""
+        row = (C.c_float * 8)(*[float(v) for v in u])
+        bsc, geo = (C.c_float * 3)(), (C.c_int * 8)()
+        check(_lib.load().bg_diffaug_decode(row, int(H), int(W), int(ops_mask), translation_ratio, cutout_ratio, bsc, geo), "bg_diffaug_decode")
+        return dict(zip(("b", "s", "c", "ty", "tx", "y0", "x0", "cy", "cx", "Sy", "Sx"), [*bsc, *geo]))
+
+    @staticmethod
+    def _check(x, y, params):
+        _f32(x, y, params)
+        assert x.dim() == 4 and x.shape == y.shape and params.numel() == 8 * x.size(0)
+        return tuple(int(v) for v in x.shape)
+
+    @staticmethod
+    def fwd(x, y, params, ops_mask, translation_ratio, cutout_ratio, linear=False):
+        """y = T(x) per sample of x [n, H, W, C] from params [n, 8] (``linear``: the linear part L, without the brightness offset)."""
+        n, H, W, Cc = diffaug._check(x, y, params)
+        check(_lib.load().bg_diffaug_f32(_ptr(x), _ptr(y), _ptr(params), n, H, W, Cc, int(ops_mask), translation_ratio, cutout_ratio,
+                                         int(bool(linear)), _stream()), "bg_diffaug_f32")
+        return y
+
+    @staticmethod
+    def adjoint(dy, dx, params, ops_mask, translation_ratio, cutout_ratio):
+        """dx = L^T dy per sample."""
+        n, H, W, Cc = diffaug._check(dy, dx, params)
+        check(_lib.load().bg_diffaug_adjoint_f32(_ptr(dy), _ptr(dx), _ptr(params), n, H, W, Cc, int(ops_mask), translation_ratio,
+                                                 cutout_ratio, _stream()), "bg_diffaug_adjoint_f32")
+        return dx
+
+
 # ------------------------------------------------------------------ spectral normalisation (include/bgan.h "spectral normalisation")
 class SpectralTable:
     """The descriptor table of one batch of wrapped layers: the rows in host memory (the calls check them before anything touches

@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 import torch
 
-from . import _lib, dist, ema as ema_mod, ops, optimizers, program
+from . import _lib, diffaugment, dist, ema as ema_mod, ops, optimizers, program
 from .gaussian_blur import Variable
 from .layers import Sequential, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
@@ -107,8 +107,9 @@ class WGAN:
                  config: TrainingConfig, *args, reproduce_vector_loss_quirk: bool = True, sync_metrics: bool = True,
                  sync_batchnorm: bool = True, merge_critic_passes: bool = True, gp_zero_norm_guard: bool = False,
                  merge_gp_filter_gradients: bool = True, step_replay: bool = True, persistent_input: bool = False,
-                 conv_math: str = "fp32", generator_ema=None, **kwargs):
+                 conv_math: str = "fp32", generator_ema=None, augment=None, **kwargs):
         ops.conv_math_code(conv_math)        # ValueError before anything is built
+        augment = diffaugment.as_augment(augment)      # ValueError likewise
         ema_schedule = ema_mod.as_schedule(generator_ema)      # ValueError likewise
         self.hparams = hyperparams
         if dist.world_size() > 1 and int(hyperparams.global_batch_size) != int(hyperparams.batch_size) * dist.world_size():
@@ -181,6 +182,13 @@ class WGAN:
         self.generator_ema = None if ema_schedule is None else ema_mod.clone_structure(self.generator)
         self.generator_ema_updates = 0
         self.conv_math = conv_math
+        # differentiable augmentation (diffaugment.py): None / a policy string / a DiffAugment.  Every batch the critic sees inside
+        # the training step -- D-step, G-step, the penalty's interpolates -- goes through a per-sample random T after the blur, and
+        # the critic's input gradient comes back through L^T.  Configuration, not state; off (None, or an empty policy): no launch
+        # and no draw is added.  self.images, generate_samples, the SWD callbacks and gradient_penalty() never see it
+        self._augment = augment
+        if augment is not None and len(self.discriminator.net().in_shape) != 3:
+            raise NotImplementedError("augment= needs a critic on [H, W, C] images")
 
     @property
     def conv_math(self):
@@ -197,6 +205,11 @@ class WGAN:
         self.discriminator.conv_math = value
         if self.generator_ema is not None:
             self.generator_ema.conv_math = value
+
+    @property
+    def augment(self):
+        """The DiffAugment in front of the critic, or None (the constructor's ``augment=``, normalised)."""
+        return self._augment
 
     # ------------------------------------------------------------------ small helpers
     @property
@@ -235,6 +248,18 @@ class WGAN:
     def _inj(self, key):
         return None if self._injected is None else self._injected.get(key)
 
+    def _aug_params(self, name, keys, B):
+        """(DiffAugment, params [len(keys) * B, 8]) for one pass of the critic, or None without augmentation: ONE draw from the
+        model's own stream for all row blocks of the pass, or the injected [B, 8] arrays ``keys`` names, stacked in that order."""
+        if self._augment is None:
+            return None
+        inj = [self._inj(k) for k in keys]
+        if any(a is not None for a in inj):
+            if any(a is None for a in inj):
+                raise ValueError(f"randomness: of {keys} either all or none are injected")
+            return self._augment, torch.cat([self._as_device(a).view(B, 8) for a in inj], 0).contiguous()
+        return self._augment, self._uniform(name, (len(keys) * B, 8))
+
     def _vec_scale(self, B):
         """Q1: the reference adds a [B] drift vector to the scalar loss, and GradientTape sums it, which
         multiplies the Wasserstein and GP gradients by the (global) batch size (wgan.py:279-285)."""
@@ -243,7 +268,8 @@ class WGAN:
     # ------------------------------------------------------------------ reference API
     def train_on_batch(self, reals, *args, randomness=None, **kwargs):
         """wgan.py:86-114.  ``randomness`` (build-side, for parity tests) injects the step's random inputs:
-        dict(z_d, z_g, alpha, mask_fake, mask_real)."""
+        dict(z_d, z_g, alpha, mask_fake, mask_real) and, with ``augment``, the [B, 8] uniforms aug_fake, aug_real, aug_hat (D-step)
+        and aug_g (G-step)."""
         self.reset_metrics()
         reals = self._as_device(reals)
         self.batch_size = int(reals.shape[0])
@@ -333,6 +359,8 @@ class WGAN:
             # recorded without the average, or on other buffers, never replays
             E = self.generator_ema.store
             key += (("generator_ema", E.theta.data_ptr(), E.state.data_ptr(), self.generator_ema_config.static_config()),)
+        if self._augment is not None:
+            key += (("augment", self._augment.static_config()),)
         return key
 
     @staticmethod
@@ -417,6 +445,8 @@ class WGAN:
         z = self._inj("z_d")
         z = self._as_device(z) if z is not None else self._uniform("z_d", (B, self.latent_size))
         fakes = G.forward(G.context(B, "g_dstep"), z, training=False)           # Q4: inference BN in the D-step
+        # one draw for every row of the step's critic passes: fakes, reals and (with the penalty) x-hat, each with its own rows
+        aug = self._aug_params("aug_d", ("aug_fake", "aug_real", "aug_hat")[:3 if self.uses_gradient_penalty else 2], B)
         masks = None
         if self._inj("mask_fake") is not None:
             masks = [torch.cat([self._as_mask(a), self._as_mask(b)], 0)
@@ -441,7 +471,7 @@ class WGAN:
             # x-hat = reals + a (fakes - reals) (wgan.py:239) joins the batch inside forward: behind the blur it is formed on the fly
             # by the one launch that blurs all three slices (bg_blur3_lerp_nhwc_f32), else bg_lerp_f32 writes it to the buffer
             s3 = D.forward(c3, [fakes, reals], training=True, masks=masks, seed=seed, lerp_alpha=self._gp_alpha(B),
-                           lerp_out=self._buf("xhat", tuple(reals.shape))).view(3 * B)
+                           lerp_out=self._buf("xhat", tuple(reals.shape)), augment=aug).view(3 * B)
             fs, rs = s3[:B], s3[B:2 * B]
             ds3 = self._buf("ds3", (3 * B,))
             ops.fill(ds3[2 * B:], 1.0)
@@ -453,26 +483,30 @@ class WGAN:
                            dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad, keep_u_rows=(2 * B, 3 * B))
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
             ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
+            aug_hat = None if aug is None else (aug[0], aug[1][2 * B:3 * B])
             if one_wgrad:
-                # delta-bar_0 goes into the x-hat rows of the pass's (blurred) input buffer, where the layer-1 filter gradient
-                # reads it beside the activations of [fakes; reals]; g itself lives in those rows and is dead after the seed
-                self._gp_v0(D, g, norms, out=c3.a0[2 * B:3 * B])
+                # delta-bar_0 goes into the x-hat rows of the pass's (blurred; with augment: augmented) input buffer, where the
+                # layer-1 filter gradient reads it beside the activations of [fakes; reals]; g itself lives in those rows (with
+                # augment: in the rows of a buffer of the pass that is dead by then) and is dead after the seed
+                self._gp_v0(D, g, norms, out=(c3.a0 if aug is None else c3.aug_input())[2 * B:3 * B], aug=aug_hat)
                 D.gp_second_order_merged(c3, 2 * B, 3 * B, reducer=red)
             else:
-                D.gp_second_order(c3.rows(2 * B, 3 * B), self._gp_v0(D, g, norms), reducer=red)
+                D.gp_second_order(c3.rows(2 * B, 3 * B), self._gp_v0(D, g, norms, aug=aug_hat), reducer=red)
         else:
             cfr = D.context(2 * B, "fr")
-            s2 = D.forward(cfr, [fakes, reals], training=True, masks=masks, seed=seed).view(2 * B)
+            s2 = D.forward(cfr, [fakes, reals], training=True, masks=masks, seed=seed,
+                           augment=None if aug is None else (aug[0], aug[1][:2 * B])).view(2 * B)
             fs, rs = s2[:B], s2[B:]
             norms = g = None
+            aug_hat = None if aug is None or not self.uses_gradient_penalty else (aug[0], aug[1][2 * B:3 * B])
             if self.uses_gradient_penalty:
-                norms, g = self._gp_first_order(reals, fakes)
+                norms, g = self._gp_first_order(reals, fakes, aug_hat)
             ds2 = self._buf("ds2", (2 * B,))
             ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds2[:B], ds2[B:], met)
             D.backward(cfr, ds2.view(2 * B, 1), need_dx=False, need_dw=True, beta=0.0, scale=1.0,
                        reducer=None if self.uses_gradient_penalty else red)
             if self.uses_gradient_penalty:
-                D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms), reducer=red)
+                D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms, aug=aug_hat), reducer=red)
         red.finish()
         D.spectral_project_gradients()
         optimizers.get_optimizer(self.discriminator).apply(store)
@@ -501,22 +535,28 @@ class WGAN:
         """d/dW of vec_scale * gp_coefficient * mean_global((n-1)^2): the second order's seed carries the whole factor."""
         return self._vec_scale(B) * float(self.hparams.gp_coefficient) * 2.0 / float(B * dist.world_size())
 
-    def _gp_v0(self, D, g, norms, out=None):
-        """The second order's input delta-bar_0: the seed of the image gradient ``g``, through the blur where the critic has one.
-        Lands in ``out`` (the x-hat rows of the merged pass's input buffer) or in a buffer of the model's own."""
+    def _gp_v0(self, D, g, norms, out=None, aug=None):
+        """The second order's input delta-bar_0: the seed of the image gradient ``g``, through the blur where the critic has one
+        and, with ``aug`` = (DiffAugment, the x-hat rows' params), through the linear part L of their augmentation: v0 =
+        L(blur(g-bar)).  Lands in ``out`` (the x-hat rows of the merged pass's input buffer) or in a buffer of the model's own."""
         own = lambda name: self._buf(name, tuple(g.shape))
         coef = self._gp_coef(int(g.shape[0]))
+        if aug is not None:
+            v = ops.gp_seed(g, norms, coef, own("gbar"), self.gp_zero_norm_guard)
+            if D.blur is not None:
+                v = D.apply_blur(v, own("v0_blur"))
+            return D.aug_linear(*aug, v, own("v0") if out is None else out)
         if D.blur is None:      # with ``out``, g is the net's own input-gradient buffer
             return ops.gp_seed(g, norms, coef, own("gbar") if out is None else out.view(g.shape), self.gp_zero_norm_guard)
         gbar = ops.gp_seed(g, norms, coef, own("gbar"), self.gp_zero_norm_guard)
         return D.apply_blur(gbar, own("v0") if out is None else out)
 
-    def _gp_first_order(self, reals, fakes):
+    def _gp_first_order(self, reals, fakes, aug=None):
         """Leaves zeta_i in the 'hat' context for the second order."""
         B = int(reals.shape[0])
         D = self.discriminator.net()
         return _first_order(D, D.context(B, "hat"), reals, fakes, self._gp_alpha(B), self._buf("xhat", tuple(reals.shape)),
-                            self._buf("ones", (B, 1)), self._buf("gp_norms", (B,)), keep_u=True)
+                            self._buf("ones", (B, 1)), self._buf("gp_norms", (B,)), keep_u=True, augment=aug)
 
     # ---- generator
     def generator_loss(self, fake_scores):
@@ -534,7 +574,7 @@ class WGAN:
         G.sync_bn = self.sync_batchnorm
         fakes = G.forward(cg, z, training=True)
         chat = D.context(B, "hat")
-        s = D.forward(chat, fakes, training=False).view(B)
+        s = D.forward(chat, fakes, training=False, augment=self._aug_params("aug_g", ("aug_g",), B)).view(B)
         ds = self._buf("ds_g", (B,))
         met = self._metrics_dev()[8:12]
         ops.wgan_g_loss(s, 1.0 / float(self.hparams.global_batch_size), ds, met)
@@ -648,11 +688,11 @@ class WGAN:
         return history
 
 
-def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms, keep_u=False):
+def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms, keep_u=False, augment=None):
     """wgan.py:234-245 on the device: x_hat, critic forward (training=False), gradient w.r.t. x_hat (through blur^T),
     per-sample L2 norms.  ``xhat``, ``ones`` and ``norms`` are the caller's buffers; returns (norms, gradient).  ``keep_u``: the
     second order follows, so LayerNormalization stages keep what its source term needs (engine.Net.backward keep_u_rows)."""
-    D.forward(ctx, ops.lerp(reals, fakes, alpha, xhat), training=False)
+    D.forward(ctx, ops.lerp(reals, fakes, alpha, xhat), training=False, augment=augment)
     g = D.backward(ctx, ops.fill(ones, 1.0), need_dx=True, need_dw=False, keep_u_rows=(0, int(reals.shape[0])) if keep_u else None)
     return ops.row_norm(g, norms), g
 

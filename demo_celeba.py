@@ -108,6 +108,9 @@ def make_parser():
                            help="average the generator's weights with this decay per generator update (off by default)")
     ema_group.add_argument("--g-ema-halflife-images", dest="g_ema_halflife_images", type=float, default=None,
                            help="average the generator's weights with a half-life of this many images (off by default)")
+    parser.add_argument("--diffaugment", default=None, metavar="POLICY",
+                        help="differentiable augmentation of every batch the critic sees: comma-separated names out of "
+                             "color, translation, cutout (off by default)")
     parser.add_argument("--swd-every-n-examples", dest="swd_every_n_examples", type=int, default=0, metavar="N",
                         help="measure the sliced Wasserstein distance between reals and fakes every N training examples on the "
                              "library's SWD kernels (0: off; the reference demo measures every 50000)")
@@ -147,7 +150,7 @@ def main(argv=None):
     elif args.g_ema_halflife_images is not None:
         generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
     gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
-                                    generator_ema=generator_ema, persistent_input=bool(args.dataset))
+                                    generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=args.diffaugment)
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)

@@ -289,6 +289,34 @@ int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int
 int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float* s, int R, int C, const float* gamma, const float* mu,
                         const float* r, float* dgamma, float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- differentiable augmentation (DiffAugment, Zhao et al. 2020) of the critic's input, NHWC fp32 -----------------------------
+ * Per sample an affine map T(x) = L x + k of its [H, W, C] map: colour, then translation, then cutout.  ops_mask: bit 0 colour,
+ * bit 1 translation, bit 2 cutout; an absent operation takes its neutral value and does no arithmetic (without colour values are
+ * copied bit for bit).  params: [n, 8] uniforms in [0, 1) per sample, decoded in float32 with one multiply per value:
+ *   b = u0 - 0.5,  s = 2 u1,  c = u2 + 0.5;
+ *   Sy = floor(H * translation_ratio + 0.5),  ty = min(floor(u3 * (2 Sy + 1)), 2 Sy) - Sy    (tx from W, u4);
+ *   cy = floor(H * cutout_ratio + 0.5),  ny = H + 1 - cy % 2,  oy = min(floor(u5 * ny), ny - 1)    (cx, nx, ox from W, u6); u7 unused.
+ * Forward, with m(p) the mean over the channels of pixel p and mu the mean over the sample:
+ *   v(p, c) = c * (s * (x(p, c) - m(p)) + m(p) - mu) + mu + b,     w(i, j) = v(i + ty, j + tx) inside the map, else 0,
+ *   y(i, j) = 0 for oy - cy / 2 <= i < oy - cy / 2 + cy and likewise in j, else w(i, j).           linear != 0: b = 0 (this is L).
+ * Adjoint, g the gradient at y:  h(i', j') = g(i' - ty, j' - tx) where that pixel is inside the map and not cut, else 0;
+ *   e = c * h + (1 - c) * mean(h),   dx(p, c) = s * e(p, c) + (1 - s) * mean_c e(p, .).
+ * Each direction is one launch that contains the sample mean; sums are taken in a fixed order without atomics (the same bits on
+ * every run).  bg_diffaug_route: *resident = 1 where a sample (H * W * C <= *resident_floats) waits in LDS between its mean and
+ * its use and is read from memory once, 0 where it is swept twice (the second read out of L2).  (Without colour there is no mean:
+ * either geometry is then one gathering sweep from memory.)  Any H, W, C >= 1; pointers 4-byte
+ * aligned (BG_ERR_BAD_ALIGNMENT), 16 bytes per lane wherever a sample's address allows.  The output must not overlap the input
+ * (BG_ERR_UNSUPPORTED); ratios outside [0, 1] and unknown mask bits: BG_ERR_UNSUPPORTED.  A refused call launches nothing.  No
+ * call takes a step-program binding: params live in device memory.
+ * bg_diffaug_decode: the decode above on the host, for one row u[8]: bsc[3] = {b, s, c}, geo[8] = {ty, tx, oy - cy / 2,
+ * ox - cx / 2, cy, cx, Sy, Sx}. */
+int bg_diffaug_route(int H, int W, int C, int* resident, int* resident_floats);
+int bg_diffaug_decode(const float* u, int H, int W, int ops_mask, float translation_ratio, float cutout_ratio, float* bsc, int* geo);
+int bg_diffaug_f32(const float* x, float* y, const float* params, int n, int H, int W, int C, int ops_mask, float translation_ratio,
+                   float cutout_ratio, int linear, void* stream);
+int bg_diffaug_adjoint_f32(const float* dy, float* dx, const float* params, int n, int H, int W, int C, int ops_mask,
+                           float translation_ratio, float cutout_ratio, void* stream);
+
 /* ---- spectral normalisation (Miyato et al. 2018; layers.SpectralNormalization) -------------------------------------------
  * A wrapped layer's kernel is the row-major matrix W[K, N] (N = the kernel's last axis, K = the rest); the engine runs on
  * W-bar = W / sigma, sigma from a running power iteration with the unit vectors u[N], v[K] (layer state).
