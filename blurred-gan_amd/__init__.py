@@ -11,15 +11,17 @@ import os as _os
 # so it is set here, before anything of the package touches the device -- and only if the launcher has not said otherwise.
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
-from . import layers, utils, dist, gaussian_blur, wgan, blurred_gan, callbacks, models, checkpoint, metrics, sliced_wasserstein, optimizers, ema, data, diffaugment  # noqa: F401
+from . import layers, utils, dist, gaussian_blur, wgan, blurred_gan, callbacks, models, checkpoint, metrics, sliced_wasserstein, optimizers, ema, data, diffaugment, objective  # noqa: F401
 from .layers import set_seed, Sequential  # noqa: F401
 from .gaussian_blur import GaussianBlur2D, blur_images  # noqa: F401
 from .wgan import WGAN, WGANGP, TrainingConfig, gradient_penalty  # noqa: F401
 from .ema import GeneratorEMA  # noqa: F401
 from .data import DeviceDataset, EpochPlan  # noqa: F401
 from .diffaugment import DiffAugment  # noqa: F401
+from .objective import Objective  # noqa: F401
 from .blurred_gan import BlurredVariant, BlurredWGANGP, BlurredWGAN  # noqa: F401
 
 __all__ = ["layers", "utils", "dist", "gaussian_blur", "wgan", "blurred_gan", "callbacks", "set_seed", "Sequential",
            "GaussianBlur2D", "blur_images", "optimizers", "WGAN", "WGANGP", "TrainingConfig", "gradient_penalty", "BlurredVariant",
-           "BlurredWGANGP", "BlurredWGAN", "ema", "GeneratorEMA", "data", "DeviceDataset", "EpochPlan", "diffaugment", "DiffAugment"]
+           "BlurredWGANGP", "BlurredWGAN", "ema", "GeneratorEMA", "data", "DeviceDataset", "EpochPlan", "diffaugment", "DiffAugment",
+           "objective", "Objective"]

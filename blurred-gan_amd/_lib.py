@@ -102,6 +102,9 @@ SIGNATURES = {
     "bg_pool2x_sum_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _i, _f, _p]),
     "bg_wgangp_d_loss": (_i, [_p, _p, _p, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
     "bg_wgan_g_loss": (_i, [_p, _i, _f, _p, _p, _p]),
+    "bg_gan_d_loss": (_i, [_p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "bg_gan_g_loss": (_i, [_p, _i, _i, _f, _p, _p, _p]),
+    "bg_gp_seed_target_f32": (_i, [_p, _p, _f, _f, _i, _p, _i, _i, _p]),
     "bg_u8_normalize_resize_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bg_u8_gather_normalize_resize_f32": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "bg_swd_ingest_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
@@ -143,6 +146,7 @@ SIGNATURES = {
 
 COMM_ID_BYTES = 128
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
+LOSS_WASSERSTEIN, LOSS_HINGE, LOSS_NONSATURATING = 0, 1, 2      # include/bgan.h bg_gan_loss
 BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*
 
 _lib = None

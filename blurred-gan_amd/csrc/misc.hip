@@ -754,6 +754,122 @@ __global__ __launch_bounds__(kT) void g_loss_kernel(const float* __restrict__ s,
   }
 }
 
+// ---------------------------------------------------------------- GAN objectives (include/bgan.h bg_gan_loss)
+// overflow-safe forms: softplus(x) = max(x, 0) + log1p(exp(-|x|)); sigmoid by the branch whose exponential cannot overflow
+__device__ inline float softplusf(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+__device__ inline float sigmoidf(float x) {
+  if (x >= 0.f) return 1.f / (1.f + expf(-x));
+  const float e = expf(x);
+  return e / (1.f + e);
+}
+
+// d_loss_kernel with the loss as a template parameter (no branch in the loop) and the penalty's target as an argument: the same
+// single workgroup, the same summation order, the same six metric slots.  LOSS == BG_LOSS_WASSERSTEIN with target 1 is
+// d_loss_kernel's arithmetic, operation for operation.
+template <int LOSS>
+__global__ __launch_bounds__(kT) void gan_d_loss_kernel(const float* __restrict__ fs, const float* __restrict__ rs,
+                                                        const float* __restrict__ norm, int B, float inv_gbs, float gp_coef,
+                                                        float gp_target, float e_drift, float vec_scale, float* dfs, float* drs,
+                                                        float* metrics) {
+  __shared__ float red[4];
+  float sf = 0.f, sr = 0.f, sn = 0.f, sg = 0.f, sl = 0.f;
+  const float w = vec_scale * inv_gbs;
+  for (int b = threadIdx.x; b < B; b += kT) {
+    const float f = fs[b], r = rs[b];
+    sf += f;
+    sr += r;
+    sn += e_drift * (fabsf(f) + fabsf(r));
+    if (norm) {
+      const float d = norm[b] - gp_target;
+      sg = fmaf(d, d, sg);
+    }
+    if (LOSS == BG_LOSS_HINGE) {             // the subgradient at the kink is 0: f == -1 and r == 1 are off
+      sl += fmaxf(1.f + f, 0.f) + fmaxf(1.f - r, 0.f);
+      dfs[b] = (f > -1.f ? w : 0.f) + e_drift * sgnf(f);
+      drs[b] = (r < 1.f ? -w : 0.f) + e_drift * sgnf(r);
+    } else if (LOSS == BG_LOSS_NONSATURATING) {
+      sl += softplusf(f) + softplusf(-r);
+      dfs[b] = w * sigmoidf(f) + e_drift * sgnf(f);
+      drs[b] = -w * sigmoidf(-r) + e_drift * sgnf(r);
+    } else {
+      dfs[b] = vec_scale * inv_gbs + e_drift * sgnf(f);
+      drs[b] = -vec_scale * inv_gbs + e_drift * sgnf(r);
+    }
+  }
+  sf = block_sum(sf, red);
+  sr = block_sum(sr, red);
+  sn = block_sum(sn, red);
+  sg = block_sum(sg, red);
+  if (LOSS != BG_LOSS_WASSERSTEIN) sl = block_sum(sl, red);
+  if (threadIdx.x == 0) {
+    const float gp = sg / (float)B;
+    const float lw = (LOSS == BG_LOSS_WASSERSTEIN ? sf - sr : sl) * inv_gbs;
+    metrics[0] = sf / (float)B;
+    metrics[1] = sr / (float)B;
+    metrics[2] = lw + gp_coef * gp + sn / (float)B;
+    metrics[3] = gp_coef * gp;
+    metrics[4] = sn / (float)B;
+    metrics[5] = gp;
+  }
+}
+
+// the generator's non-saturating loss: sum softplus(-s) / gbs, d/ds = -sigmoid(-s) / gbs
+__global__ __launch_bounds__(kT) void g_loss_ns_kernel(const float* __restrict__ s, int B, float inv_gbs, float* ds, float* metrics) {
+  __shared__ float red[4];
+  float ss = 0.f, sl = 0.f;
+  for (int b = threadIdx.x; b < B; b += kT) {
+    const float v = s[b];
+    ss += v;
+    sl += softplusf(-v);
+    ds[b] = -inv_gbs * sigmoidf(-v);
+  }
+  ss = block_sum(ss, red);
+  sl = block_sum(sl, red);
+  if (threadIdx.x == 0) {
+    metrics[0] = ss / (float)B;
+    metrics[1] = sl * inv_gbs;
+  }
+}
+
+// out = coef * ((n - t) / n) * g, the seed of d mean((n - t)^2) / dg.  MODE 0 is t == 0: coef * g with no division, so a sample
+// of zero norm gives 0; MODE 1 is gp_seed_kernel<false>'s expression with t in place of 1 (NaN at a zero norm, as the reference),
+// MODE 2 gp_seed_kernel<true>'s.  VEC: out and g are 16-byte aligned and n_per % 4 == 0, so a float4 never straddles two samples.
+// out may BE g (the step writes the seed over the gradient it came from): neither is __restrict__.
+template <int MODE>
+__device__ inline float seed_factor(float n, float coef, float t) {
+  if (MODE == 0) return coef;
+  return coef * ((n - t) / n);
+}
+
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(kT) void gp_seed_target_kernel(const float* g, const float* __restrict__ norm, float coef, float target,
+                                                            float* out, size_t total, int n_per) {
+  const size_t tid = (size_t)blockIdx.x * kT + threadIdx.x, nth = (size_t)gridDim.x * kT;
+  if (VEC) {
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* o4 = reinterpret_cast<float4*>(out);
+    const size_t total4 = total / 4, per4 = (size_t)(n_per / 4);
+    for (size_t q = tid; q < total4; q += nth) {
+      const float n = MODE == 0 ? 0.f : norm[q / per4];
+      const float4 v = g4[q];
+      float4 o;
+      if (MODE == 2 && n == 0.f) {
+        o = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        const float s = seed_factor<MODE>(n, coef, target);
+        o = make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
+      }
+      o4[q] = o;
+    }
+  } else {
+    for (size_t e = tid; e < total; e += nth) {
+      const float n = MODE == 0 ? 0.f : norm[e / n_per];
+      out[e] = (MODE == 2 && n == 0.f) ? 0.f : seed_factor<MODE>(n, coef, target) * g[e];
+    }
+  }
+}
+
 // ---------------------------------------------------------------- input pipeline: u8 -> normalised f32 (+ bilinear resize)
 __global__ __launch_bounds__(kT) void u8_normalize_resize_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, size_t total,
                                                                  int Hs, int Ws, int C, int Hd, int Wd, float sy, float sx) {
@@ -1220,6 +1336,58 @@ int bg_wgan_g_loss(const float* s, int B, float inv_gbs, float* ds, float* metri
   bg::Launch L(stream, "g_loss", 0, 0);
   bg::launch(g_loss_kernel, dim3(1), dim3(kT), 0, L.s, s, B, inv_gbs, ds, metrics_d);
   return L.done("g_loss_kernel");
+}
+
+#define BG_REQUIRE_LOSS(fn, loss)                                                                                          \
+  BG_REQUIRE((loss) == BG_LOSS_WASSERSTEIN || (loss) == BG_LOSS_HINGE || (loss) == BG_LOSS_NONSATURATING, BG_ERR_UNSUPPORTED, \
+             fn ": unknown loss %d", (int)(loss))
+
+int bg_gan_d_loss(const float* fs, const float* rs, const float* norm_b, int B, int loss, float inv_gbs, float gp_coef, float gp_target,
+                  float e_drift, float vec_scale, float* dfs, float* drs, float* metrics_d, void* stream) {
+  BG_POINTWISE_PROLOGUE("bg_gan_d_loss", fs && rs && dfs && drs && metrics_d, B);
+  BG_REQUIRE_LOSS("bg_gan_d_loss", loss);
+  BG_REQUIRE(gp_target >= 0.f, BG_ERR_UNSUPPORTED, "bg_gan_d_loss: gp_target=%g (must be >= 0)", gp_target);
+  bg::Launch L(stream, "gan_d_loss", 0, 0);
+  auto go = [&](auto kern) {
+    bg::launch(kern, dim3(1), dim3(kT), 0, L.s, fs, rs, norm_b, B, inv_gbs, gp_coef, gp_target, e_drift, vec_scale, dfs, drs, metrics_d);
+  };
+  if (loss == BG_LOSS_HINGE) go(gan_d_loss_kernel<BG_LOSS_HINGE>);
+  else if (loss == BG_LOSS_NONSATURATING) go(gan_d_loss_kernel<BG_LOSS_NONSATURATING>);
+  else go(gan_d_loss_kernel<BG_LOSS_WASSERSTEIN>);
+  return L.done("gan_d_loss_kernel");
+}
+
+int bg_gan_g_loss(const float* s, int B, int loss, float inv_gbs, float* ds, float* metrics_d, void* stream) {
+  BG_POINTWISE_PROLOGUE("bg_gan_g_loss", s && ds && metrics_d, B);
+  BG_REQUIRE_LOSS("bg_gan_g_loss", loss);
+  bg::Launch L(stream, "gan_g_loss", 0, 0);
+  if (loss == BG_LOSS_NONSATURATING) bg::launch(g_loss_ns_kernel, dim3(1), dim3(kT), 0, L.s, s, B, inv_gbs, ds, metrics_d);
+  else bg::launch(g_loss_kernel, dim3(1), dim3(kT), 0, L.s, s, B, inv_gbs, ds, metrics_d);
+  return L.done("gan_g_loss_kernel");
+}
+
+int bg_gp_seed_target_f32(const float* g, const float* norm_b, float coef, float target, int guard, float* out, int B, int n_per,
+                          void* stream) {
+  BG_REQUIRE(g && norm_b && out, BG_ERR_NULL, "bg_gp_seed_target_f32: null pointer");
+  BG_REQUIRE(B > 0 && n_per > 0, BG_ERR_BAD_SHAPE, "bg_gp_seed_target_f32: B=%d n_per=%d", B, n_per);
+  BG_REQUIRE(target >= 0.f, BG_ERR_UNSUPPORTED, "bg_gp_seed_target_f32: target=%g (must be >= 0)", target);
+  const size_t total = (size_t)B * n_per;
+  const bool vec = (n_per & 3) == 0 && bg::aligned16(g) && bg::aligned16(out);
+  const int mode = target == 0.f ? 0 : (guard ? 2 : 1);
+  bg::Launch L(stream, "gp_seed_target", 0, 8.0 * total);
+  auto go = [&](auto kern) {
+    bg::launch(kern, dim3(grid_for(total, vec ? 4 : 1)), dim3(kT), 0, L.s, g, norm_b, coef, target, out, total, n_per);
+  };
+  if (vec) {
+    if (mode == 0) go(gp_seed_target_kernel<0, true>);
+    else if (mode == 1) go(gp_seed_target_kernel<1, true>);
+    else go(gp_seed_target_kernel<2, true>);
+  } else {
+    if (mode == 0) go(gp_seed_target_kernel<0, false>);
+    else if (mode == 1) go(gp_seed_target_kernel<1, false>);
+    else go(gp_seed_target_kernel<2, false>);
+  }
+  return L.done("gp_seed_target_kernel");
 }
 
 int bg_u8_normalize_resize_f32(const uint8_t* src, float* dst, int B, int Hs, int Ws, int C, int Hd, int Wd, void* stream) {

@@ -619,6 +619,38 @@ def wgan_g_loss(s, inv_gbs, ds, metrics):
     check(_lib.load().bg_wgan_g_loss(_ptr(s), s.numel(), inv_gbs, _ptr(ds), _ptr(metrics), _stream()), "bg_wgan_g_loss")
 
 
+class objective:
+    """The GAN-objective kernels (include/bgan.h bg_gan_loss).  A namespace for the reason ``layernorm`` is one: the engine-trace
+    maker knows the module's public functions by name, and the default objective launches none of these."""
+
+    LOSS = {"wasserstein": _lib.LOSS_WASSERSTEIN, "hinge": _lib.LOSS_HINGE, "nonsaturating": _lib.LOSS_NONSATURATING}
+
+    @staticmethod
+    def d_loss(fs, rs, norm_b, loss, inv_gbs, gp_coef, gp_target, e_drift, vec_scale, dfs, drs, metrics):
+        """``wgangp_d_loss`` for the loss code ``loss`` and the penalty target ``gp_target``."""
+        _f32(fs, rs, norm_b, dfs, drs, metrics)
+        B = fs.numel()
+        assert rs.numel() == B == dfs.numel() == drs.numel() and metrics.numel() >= 6 and (norm_b is None or norm_b.numel() == B)
+        check(_lib.load().bg_gan_d_loss(_ptr(fs), _ptr(rs), _ptr(norm_b), B, int(loss), inv_gbs, gp_coef, gp_target, e_drift, vec_scale,
+                                        _ptr(dfs), _ptr(drs), _ptr(metrics), _stream()), "bg_gan_d_loss")
+
+    @staticmethod
+    def g_loss(s, loss, inv_gbs, ds, metrics):
+        _f32(s, ds, metrics)
+        assert ds.numel() == s.numel() and metrics.numel() >= 2
+        check(_lib.load().bg_gan_g_loss(_ptr(s), s.numel(), int(loss), inv_gbs, _ptr(ds), _ptr(metrics), _stream()), "bg_gan_g_loss")
+
+    @staticmethod
+    def gp_seed(g, norm_b, coef, target, out, zero_norm_guard=False):
+        """out = coef * (n - target) / n * g per sample; ``out`` may be ``g``."""
+        _f32(g, norm_b, out)
+        B = g.shape[0]
+        assert out.numel() == g.numel() and norm_b.numel() == B
+        check(_lib.load().bg_gp_seed_target_f32(_ptr(g), _ptr(norm_b), coef, target, int(bool(zero_norm_guard)), _ptr(out), B,
+                                                g.numel() // B, _stream()), "bg_gp_seed_target_f32")
+        return out
+
+
 def u8_normalize_resize(src_u8, dst):
     """uint8 NHWC -> float32 NHWC in [-1, 1], bilinear-resized to dst's spatial size (demo_celeba.py:22-35)."""
     assert src_u8.dtype == torch.uint8 and dst.dtype == torch.float32

@@ -15,7 +15,7 @@ from typing import List
 import numpy as np
 import torch
 
-from . import _lib, diffaugment, dist, ema as ema_mod, ops, optimizers, program
+from . import _lib, diffaugment, dist, ema as ema_mod, objective as objective_mod, ops, optimizers, program
 from .gaussian_blur import Variable
 from .layers import Sequential, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
@@ -107,10 +107,11 @@ class WGAN:
                  config: TrainingConfig, *args, reproduce_vector_loss_quirk: bool = True, sync_metrics: bool = True,
                  sync_batchnorm: bool = True, merge_critic_passes: bool = True, gp_zero_norm_guard: bool = False,
                  merge_gp_filter_gradients: bool = True, step_replay: bool = True, persistent_input: bool = False,
-                 conv_math: str = "fp32", generator_ema=None, augment=None, **kwargs):
+                 conv_math: str = "fp32", generator_ema=None, augment=None, objective=None, **kwargs):
         ops.conv_math_code(conv_math)        # ValueError before anything is built
         augment = diffaugment.as_augment(augment)      # ValueError likewise
         ema_schedule = ema_mod.as_schedule(generator_ema)      # ValueError likewise
+        objective = objective_mod.as_objective(objective, self.uses_gradient_penalty)      # ValueError likewise
         self.hparams = hyperparams
         if dist.world_size() > 1 and int(hyperparams.global_batch_size) != int(hyperparams.batch_size) * dist.world_size():
             import warnings
@@ -187,6 +188,10 @@ class WGAN:
         # the critic's input gradient comes back through L^T.  Configuration, not state; off (None, or an empty policy): no launch
         # and no draw is added.  self.images, generate_samples, the SWD callbacks and gradient_penalty() never see it
         self._augment = augment
+        # the objective (objective.py): None / a loss name / an Objective.  The reference objective runs the reference's loss kernels,
+        # launch for launch; any other goes through bg_gan_d_loss / bg_gan_g_loss / bg_gp_seed_target_f32, and with penalty_interval
+        # k > 1 only every k-th critic step carries the penalty.  Configuration, not state: the phase is n_batches % k
+        self._objective = objective
         if augment is not None and len(self.discriminator.net().in_shape) != 3:
             raise NotImplementedError("augment= needs a critic on [H, W, C] images")
 
@@ -210,6 +215,16 @@ class WGAN:
     def augment(self):
         """The DiffAugment in front of the critic, or None (the constructor's ``augment=``, normalised)."""
         return self._augment
+
+    @property
+    def objective(self):
+        """The training objective (the constructor's ``objective=``, normalised to an Objective)."""
+        return self._objective
+
+    def _penalty_this_step(self):
+        """Whether the critic step of the batch at hand carries the gradient penalty: the class has one, and the objective's
+        interval says so (n_batches counts the finished batches)."""
+        return self.uses_gradient_penalty and self._objective.penalty_at(self.n_batches)
 
     # ------------------------------------------------------------------ small helpers
     @property
@@ -353,7 +368,10 @@ class WGAN:
                # spectral normalisation: the rounds per step, and whether the effective weights are stale on their own (a round taken by
                # hand between two steps clears sn_dirty and leaves tr_dirty: the step then skips a refresh a recorded program holds)
                G.spectral_rounds, D.spectral_rounds, G.store.sn_dirty, D.store.sn_dirty,
-               self._optimizer_key(self.generator), self._optimizer_key(self.discriminator))
+               self._optimizer_key(self.generator), self._optimizer_key(self.discriminator),
+               # with penalty_interval k > 1 the critic steps with and without penalty are two programs that alternate and both
+               # replay; the generator's step does not depend on the phase
+               ("objective", self._objective.static_config(), self._penalty_this_step() if kind == "d" else None))
         if self.generator_ema is not None:
             # the averaged model's presence, the two buffers the update writes and the schedule's static configuration: a program
             # recorded without the average, or on other buffers, never replays
@@ -431,8 +449,15 @@ class WGAN:
 
     # ---- discriminator
     def discriminator_loss(self, reals, fakes, real_scores, fake_scores):
-        """wgan.py:128-130 (value only; the training step uses the fused device path)."""
-        return (fake_scores - real_scores).sum() * (1.0 / self.hparams.global_batch_size)
+        """wgan.py:128-130 (value only; the training step uses the fused device path), for the model's objective."""
+        loss = self._objective.loss
+        if loss == "hinge":
+            terms = torch.relu(1.0 + fake_scores) + torch.relu(1.0 - real_scores)
+        elif loss == "nonsaturating":
+            terms = torch.nn.functional.softplus(fake_scores) + torch.nn.functional.softplus(-real_scores)
+        else:
+            terms = fake_scores - real_scores
+        return terms.sum() * (1.0 / self.hparams.global_batch_size)
 
     def discriminator_step(self, reals):
         """wgan.py:132-151."""
@@ -446,13 +471,17 @@ class WGAN:
         z = self._as_device(z) if z is not None else self._uniform("z_d", (B, self.latent_size))
         fakes = G.forward(G.context(B, "g_dstep"), z, training=False)           # Q4: inference BN in the D-step
         # one draw for every row of the step's critic passes: fakes, reals and (with the penalty) x-hat, each with its own rows
-        aug = self._aug_params("aug_d", ("aug_fake", "aug_real", "aug_hat")[:3 if self.uses_gradient_penalty else 2], B)
+        # penalty: this step carries the gradient penalty.  A WGANGP between two penalty steps of a lazy objective takes the
+        # two-slice path of the plain WGAN -- no x-hat, no first or second order, no alpha or aug_hat draw -- with its own drift
+        # term and vector-loss scale
+        penalty = self._penalty_this_step()
+        aug = self._aug_params("aug_d", ("aug_fake", "aug_real", "aug_hat")[:3 if penalty else 2], B)
         masks = None
         if self._inj("mask_fake") is not None:
             masks = [torch.cat([self._as_mask(a), self._as_mask(b)], 0)
                      for a, b in zip(self._inj("mask_fake"), self._inj("mask_real"))]
         inv_gbs = 1.0 / float(hp.global_batch_size)
-        gp_c = float(getattr(hp, "gp_coefficient", 0.0)) if self.uses_gradient_penalty else 0.0
+        gp_c = float(getattr(hp, "gp_coefficient", 0.0)) * self._objective.penalty_interval if penalty else 0.0
         e_d = float(getattr(hp, "e_drift", 0.0)) if self.uses_gradient_penalty else 0.0
         met = self._metrics_dev()[:8]
         vs = self._vec_scale(B)
@@ -460,7 +489,7 @@ class WGAN:
         store.ensure_opt_state()
         red = dist.GradReducer(store.grad, store.n_train)       # buckets go out while the backward is still running
         seed = self._rng_seed + 104729 * (dist.rank() + 1)
-        merged = (self.uses_gradient_penalty and self.merge_critic_passes and all(st.bn is None for st in D.stages))
+        merged = (penalty and self.merge_critic_passes and all(st.bn is None for st in D.stages))
         if merged:
             # [fakes; reals] (training=True: Dropout) and x-hat (training=False) share every weight: ONE 3B-sample pass forward
             # and ONE backward, the Dropout masks covering the first 2B samples only (bg_epilogue.keep_elems).  The seeds of
@@ -475,14 +504,14 @@ class WGAN:
             fs, rs = s3[:B], s3[B:2 * B]
             ds3 = self._buf("ds3", (3 * B,))
             ops.fill(ds3[2 * B:], 1.0)
-            ops.wgangp_d_loss(fs, rs, None, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)      # seeds only; metrics below
+            self._d_loss(fs, rs, None, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)      # seeds only; metrics below
             # a critic with LayerNormalization stages takes the separate second-order route whatever the switch says: the merged one
             # overwrites the x-hat rows of the activations that the stages' source backward reads (engine.gp_second_order_merged)
             one_wgrad = self.merge_gp_filter_gradients and not D.has_ln
             g = D.backward(c3, ds3.view(3 * B, 1), need_dx=True, need_dw=True, beta=0.0, scale=1.0, dw_rows=2 * B,
                            dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad, keep_u_rows=(2 * B, 3 * B))
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
-            ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
+            self._d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
             aug_hat = None if aug is None else (aug[0], aug[1][2 * B:3 * B])
             if one_wgrad:
                 # delta-bar_0 goes into the x-hat rows of the pass's (blurred; with augment: augmented) input buffer, where the
@@ -498,14 +527,14 @@ class WGAN:
                            augment=None if aug is None else (aug[0], aug[1][:2 * B])).view(2 * B)
             fs, rs = s2[:B], s2[B:]
             norms = g = None
-            aug_hat = None if aug is None or not self.uses_gradient_penalty else (aug[0], aug[1][2 * B:3 * B])
-            if self.uses_gradient_penalty:
+            aug_hat = None if aug is None or not penalty else (aug[0], aug[1][2 * B:3 * B])
+            if penalty:
                 norms, g = self._gp_first_order(reals, fakes, aug_hat)
             ds2 = self._buf("ds2", (2 * B,))
-            ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds2[:B], ds2[B:], met)
+            self._d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds2[:B], ds2[B:], met)
             D.backward(cfr, ds2.view(2 * B, 1), need_dx=False, need_dw=True, beta=0.0, scale=1.0,
-                       reducer=None if self.uses_gradient_penalty else red)
-            if self.uses_gradient_penalty:
+                       reducer=None if penalty else red)
+            if penalty:
                 D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms, aug=aug_hat), reducer=red)
         red.finish()
         D.spectral_project_gradients()
@@ -520,6 +549,19 @@ class WGAN:
     def _record_gp_metrics(self, m):
         pass
 
+    def _d_loss(self, fs, rs, norms, inv_gbs, gp_c, e_d, vs, dfs, drs, met):
+        """The critic's loss launch: the reference objective through the reference's kernel, any other through bg_gan_d_loss."""
+        obj = self._objective
+        if obj.is_reference:
+            return ops.wgangp_d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, dfs, drs, met)
+        return ops.objective.d_loss(fs, rs, norms, ops.objective.LOSS[obj.loss], inv_gbs, gp_c, obj.penalty_target, e_d, vs, dfs, drs, met)
+
+    def _gp_seed(self, g, norms, coef, out):
+        obj = self._objective
+        if obj.is_reference:
+            return ops.gp_seed(g, norms, coef, out, self.gp_zero_norm_guard)
+        return ops.objective.gp_seed(g, norms, coef, obj.penalty_target, out, self.gp_zero_norm_guard)
+
     @staticmethod
     def _as_mask(a):
         if isinstance(a, np.ndarray):
@@ -527,13 +569,19 @@ class WGAN:
         return a.to(torch.uint8)
 
     def _gp_alpha(self, B):
-        """The interpolation weights of x-hat (wgan.py:237): injected, or drawn."""
+        """The interpolation weights of x-hat (wgan.py:237): injected, or drawn; where the objective puts the penalty on the reals
+        or on the fakes, the constant 0 or 1, written by a launch (a step program records it) with nothing drawn or injected."""
+        const = self._objective.penalty_alpha
+        if const is not None:
+            return ops.fill(self._buf("alpha", (B,)), const)
         a = self._inj("alpha")
         return self._as_device(a).view(B) if a is not None else self._uniform("alpha", (B,))
 
     def _gp_coef(self, B):
-        """d/dW of vec_scale * gp_coefficient * mean_global((n-1)^2): the second order's seed carries the whole factor."""
-        return self._vec_scale(B) * float(self.hparams.gp_coefficient) * 2.0 / float(B * dist.world_size())
+        """d/dW of vec_scale * gp_coefficient * mean_global((n-1)^2): the second order's seed carries the whole factor (a lazy
+        objective: times its interval, on the steps that carry the penalty)."""
+        k = self._objective.penalty_interval
+        return self._vec_scale(B) * float(self.hparams.gp_coefficient) * k * 2.0 / float(B * dist.world_size())
 
     def _gp_v0(self, D, g, norms, out=None, aug=None):
         """The second order's input delta-bar_0: the seed of the image gradient ``g``, through the blur where the critic has one
@@ -542,13 +590,13 @@ class WGAN:
         own = lambda name: self._buf(name, tuple(g.shape))
         coef = self._gp_coef(int(g.shape[0]))
         if aug is not None:
-            v = ops.gp_seed(g, norms, coef, own("gbar"), self.gp_zero_norm_guard)
+            v = self._gp_seed(g, norms, coef, own("gbar"))
             if D.blur is not None:
                 v = D.apply_blur(v, own("v0_blur"))
             return D.aug_linear(*aug, v, own("v0") if out is None else out)
         if D.blur is None:      # with ``out``, g is the net's own input-gradient buffer
-            return ops.gp_seed(g, norms, coef, own("gbar") if out is None else out.view(g.shape), self.gp_zero_norm_guard)
-        gbar = ops.gp_seed(g, norms, coef, own("gbar"), self.gp_zero_norm_guard)
+            return self._gp_seed(g, norms, coef, own("gbar") if out is None else out.view(g.shape))
+        gbar = self._gp_seed(g, norms, coef, own("gbar"))
         return D.apply_blur(gbar, own("v0") if out is None else out)
 
     def _gp_first_order(self, reals, fakes, aug=None):
@@ -560,7 +608,9 @@ class WGAN:
 
     # ---- generator
     def generator_loss(self, fake_scores):
-        """wgan.py:155-157."""
+        """wgan.py:155-157, for the model's objective."""
+        if self._objective.loss == "nonsaturating":
+            return torch.nn.functional.softplus(-fake_scores).sum() * (1.0 / self.hparams.global_batch_size)
         return -fake_scores.sum() * (1.0 / self.hparams.global_batch_size)
 
     def generator_step(self):
@@ -577,7 +627,10 @@ class WGAN:
         s = D.forward(chat, fakes, training=False, augment=self._aug_params("aug_g", ("aug_g",), B)).view(B)
         ds = self._buf("ds_g", (B,))
         met = self._metrics_dev()[8:12]
-        ops.wgan_g_loss(s, 1.0 / float(self.hparams.global_batch_size), ds, met)
+        if self._objective.is_reference:
+            ops.wgan_g_loss(s, 1.0 / float(self.hparams.global_batch_size), ds, met)
+        else:
+            ops.objective.g_loss(s, ops.objective.LOSS[self._objective.loss], 1.0 / float(self.hparams.global_batch_size), ds, met)
         dfakes = D.backward(chat, ds.view(B, 1), need_dx=True, need_dw=False)
         store = self.generator.store
         store.ensure_opt_state()
@@ -697,8 +750,10 @@ def _first_order(D, ctx, reals, fakes, alpha, xhat, ones, norms, keep_u=False, a
     return ops.row_norm(g, norms), g
 
 
-def gradient_penalty(discriminator, reals, fakes, alpha=None):
-    """wgan.py:234-246 (value only): mean((||d D(x_hat)/d x_hat|| - 1)^2) on the HIP kernels."""
+def gradient_penalty(discriminator, reals, fakes, alpha=None, target=1.0):
+    """wgan.py:234-246 (value only): mean((||d D(x_hat)/d x_hat|| - target)^2) on the HIP kernels."""
+    if not (isinstance(target, numbers.Real) and target >= 0.0):
+        raise ValueError(f"gradient_penalty: `target` must be a number >= 0, got {target!r}")
     D = discriminator.net()
     dev = D.device
     reals = reals.to(dev, torch.float32).contiguous()
@@ -712,7 +767,10 @@ def gradient_penalty(discriminator, reals, fakes, alpha=None):
     # mean((n - 1)^2) by the loss kernel itself (metric slot 5 of bg_wgangp_d_loss), not by torch arithmetic
     zero = ops.fill(torch.empty(B, dtype=torch.float32, device=dev), 0.0)
     scratch, met = torch.empty(2, B, dtype=torch.float32, device=dev), torch.empty(8, dtype=torch.float32, device=dev)
-    ops.wgangp_d_loss(zero, zero, n, 1.0, 0.0, 0.0, 1.0, scratch[0], scratch[1], met)
+    if float(target) == 1.0:
+        ops.wgangp_d_loss(zero, zero, n, 1.0, 0.0, 0.0, 1.0, scratch[0], scratch[1], met)
+    else:
+        ops.objective.d_loss(zero, zero, n, ops.objective.LOSS["wasserstein"], 1.0, 0.0, float(target), 0.0, 1.0, scratch[0], scratch[1], met)
     return met[5]
 
 
@@ -741,8 +799,11 @@ class WGANGP(WGAN):
         self.norm_term_metric(m[4])
 
     def discriminator_loss(self, reals, fakes, real_scores, fake_scores):
-        """wgan.py:272-285 (value only): a [B] vector, as in the reference."""
+        """wgan.py:272-285 (value only): a [B] vector, as in the reference.  The penalty is the objective's -- its target, at its
+        points -- with the plain coefficient: what a lazy objective adds per step on average."""
         loss = super().discriminator_loss(reals, fakes, real_scores, fake_scores)
-        gp_term = self.hparams.gp_coefficient * gradient_penalty(self.discriminator, reals, fakes)
+        obj = self._objective
+        alpha = None if obj.penalty_alpha is None else torch.full((int(reals.shape[0]),), obj.penalty_alpha, device=self.device)
+        gp_term = self.hparams.gp_coefficient * gradient_penalty(self.discriminator, reals, fakes, alpha, obj.penalty_target)
         norm_term = self.hparams.e_drift * (fake_scores.abs().view(-1) + real_scores.abs().view(-1))
         return loss + gp_term + norm_term

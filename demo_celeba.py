@@ -111,6 +111,16 @@ def make_parser():
     parser.add_argument("--diffaugment", default=None, metavar="POLICY",
                         help="differentiable augmentation of every batch the critic sees: comma-separated names out of "
                              "color, translation, cutout (off by default)")
+    parser.add_argument("--loss", default="wasserstein", choices=["wasserstein", "hinge", "nonsaturating"],
+                        help="the pair of critic and generator losses: wasserstein (default, the reference's), hinge or the "
+                             "non-saturating logistic loss")
+    parser.add_argument("--penalty-on", dest="penalty_on", default="interpolates", choices=["interpolates", "reals", "fakes"],
+                        help="where the critic's input gradient is penalised: the interpolates of reals and fakes (default, the "
+                             "reference's), the reals (with --penalty-target 0: R1) or the fakes (R2)")
+    parser.add_argument("--penalty-target", dest="penalty_target", type=float, default=1.0,
+                        help="the gradient norm the penalty pulls towards: gp_coefficient * mean((norm - target)^2)")
+    parser.add_argument("--penalty-interval", dest="penalty_interval", type=int, default=1, metavar="K",
+                        help="lazy regularisation: the penalty runs on every K-th critic step with K times the coefficient")
     parser.add_argument("--swd-every-n-examples", dest="swd_every_n_examples", type=int, default=0, metavar="N",
                         help="measure the sliced Wasserstein distance between reals and fakes every N training examples on the "
                              "library's SWD kernels (0: off; the reference demo measures every 50000)")
@@ -150,7 +160,8 @@ def main(argv=None):
     elif args.g_ema_halflife_images is not None:
         generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
     gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
-                                    generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=args.diffaugment)
+                                    generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=args.diffaugment,
+                                    objective=blurred_gan.Objective(args.loss, args.penalty_target, args.penalty_on, args.penalty_interval))
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:
         manager.restore(manager.latest_checkpoint)

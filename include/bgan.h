@@ -404,6 +404,34 @@ int bg_wgangp_d_loss(const float* fs, const float* rs, const float* norm_b, int 
 /* metrics_d[0] = mean(s), metrics_d[1] = -sum(s)*inv_gbs ; ds[b] = -inv_gbs */
 int bg_wgan_g_loss(const float* s, int B, float inv_gbs, float* ds, float* metrics_d, void* stream);
 
+/* ---- GAN objectives: the loss as an argument, the penalty's target as an argument -----------------------------------------
+ * With s+ = softplus, sums scaled by inv_gbs:
+ *   BG_LOSS_WASSERSTEIN    critic sum(fs - rs)                         generator -sum(fs)
+ *   BG_LOSS_HINGE          critic sum(relu(1 + fs) + relu(1 - rs))     generator -sum(fs)
+ *   BG_LOSS_NONSATURATING  critic sum(s+(fs) + s+(-rs))                generator sum(s+(-fs))
+ * Softplus is max(x, 0) + log1p(exp(-|x|)) and the sigmoid takes the branch whose exponential cannot overflow: finite at any
+ * score.  The hinge's subgradient at its kink is 0 (fs == -1 and rs == 1 are off).  Refused calls (BG_ERR_NULL: null pointer;
+ * BG_ERR_BAD_SHAPE: B <= 0, n_per <= 0; BG_ERR_UNSUPPORTED: unknown loss, target < 0) launch nothing.  None takes a
+ * step-program binding. */
+typedef enum { BG_LOSS_WASSERSTEIN = 0, BG_LOSS_HINGE = 1, BG_LOSS_NONSATURATING = 2 } bg_gan_loss;
+/* bg_wgangp_d_loss for any loss and penalty target t: one workgroup, the same summation order, the same six metric slots with
+ * metrics_d[5] = mean((n - t)^2) (0 without norm_b) and the loss of the table in metrics_d[2].  Seeds, w = vec_scale * inv_gbs:
+ *   wasserstein    dfs = w + e_drift*sign(fs)                     drs = -w + e_drift*sign(rs)
+ *   hinge          dfs = (fs > -1 ? w : 0) + e_drift*sign(fs)     drs = (rs < 1 ? -w : 0) + e_drift*sign(rs)
+ *   nonsaturating  dfs = w*sigmoid(fs) + e_drift*sign(fs)         drs = -w*sigmoid(-rs) + e_drift*sign(rs)
+ * BG_LOSS_WASSERSTEIN with gp_target 1 is bg_wgangp_d_loss bit for bit. */
+int bg_gan_d_loss(const float* fs, const float* rs, const float* norm_b /* may be NULL */, int B, int loss, float inv_gbs, float gp_coef,
+                  float gp_target, float e_drift, float vec_scale, float* dfs, float* drs, float* metrics_d, void* stream);
+/* nonsaturating: ds = -inv_gbs*sigmoid(-s), metrics_d[1] = sum(s+(-s))*inv_gbs; the other two losses: bg_wgan_g_loss.
+ * metrics_d[0] = mean(s). */
+int bg_gan_g_loss(const float* s, int B, int loss, float inv_gbs, float* ds, float* metrics_d, void* stream);
+/* second-order seed for the target t >= 0: out[b,:] = coef * (norm[b]-t)/norm[b] * g[b,:].  t == 0 runs an instantiation that
+ * computes coef * g with no division (a zero-norm sample gives 0, never NaN, whatever guard says); for t > 0, guard != 0 is
+ * bg_gp_seed_guarded_f32's subgradient 0 at a zero norm, guard == 0 bg_gp_seed_f32's NaN, and t == 1 equals those calls bit for
+ * bit.  float4 where out and g are 16-byte aligned and n_per % 4 == 0, one float at a time otherwise.  out may be g. */
+int bg_gp_seed_target_f32(const float* g, const float* norm_b, float coef, float target, int guard, float* out, int B, int n_per,
+                          void* stream);
+
 /* ---- input pipeline (demo_celeba.py:22-35, demo_mnist.py:24-31): uint8 NHWC -> float32, (x - 127.5) / 127.5, then
  *      tf.image.resize(bilinear, half-pixel centres) to [Hd, Wd] (normalise BEFORE resize, aspect not preserved).
  *      Hd == Hs && Wd == Ws is the MNIST pipeline (normalise only). */
