@@ -80,6 +80,7 @@ SIGNATURES = {
     "bg_ln_tangent_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p]),
     "bg_ln_gp_source_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _f, _p, _z, _p]),
     "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "bg_diffaug_plan": (_i, [_i, _i, _i, _i, _i] + [C.POINTER(_i)] * 5),
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
     "bg_diffaug_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "bg_diffaug_adjoint_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),

@@ -236,6 +236,33 @@ __global__ __launch_bounds__(kTBig, 8) void diffaug_kernel(const float* __restri
 
 inline bool resident(size_t E) { return E <= (size_t)kResident; }
 
+// What run() launches for n samples of E floats: the one place that decides (bg_diffaug_plan reports it).
+struct LaunchPlan { bool resident; unsigned threads, gx, gy; size_t lds; };
+
+inline LaunchPlan plan_for(int n, size_t E, int ops_mask) {
+  const bool color = (ops_mask & OP_COLOR) != 0;
+  LaunchPlan p;
+  p.gx = (unsigned)std::min(n, kMaxBlocks);
+  p.gy = 1;
+  p.threads = color && E >= (size_t)kBigFloats ? kTBig : kTSmall;
+  const size_t red_bytes = kMaxWaves * sizeof(float);
+  // (without colour there is no mean to wait for: every sample size is one gathering sweep straight from memory)
+  p.resident = resident(E) && color;
+  if (p.resident) {
+    // the image's room: the sample, the alignment pad in front of it, rounded up to whole float4s
+    p.lds = red_bytes + (E + 3 + 3) / 4 * 16;
+  } else {
+    // a small batch of large images is cut along the sample until the chip has two workgroups per compute unit: with colour every
+    // workgroup of a sample repeats sweep 1, so no further.  Without colour a cut costs nothing: 256-thread workgroups, eight per
+    // compute unit, at least a quarter of a chunk each
+    const unsigned want = color ? 512u : 2048u;
+    unsigned gy = (unsigned)std::min<size_t>(std::max<size_t>(E / (color ? kChunkFloats : kChunkFloats / 4), 1), 64);
+    p.gy = std::min(gy, std::max(1u, want / p.gx));
+    p.lds = red_bytes;
+  }
+  return p;
+}
+
 int run(bool adj, const float* in, float* out, const float* params, int n, int H, int W, int C, int ops_mask, float translation_ratio,
         float cutout_ratio, int linear, void* stream, const char* what) {
   BG_REQUIRE(in && out && params, BG_ERR_NULL, "%s: null pointer", what);
@@ -255,26 +282,15 @@ int run(bool adj, const float* in, float* out, const float* params, int n, int H
   g.ops = ops_mask; g.linear = linear ? 1 : 0;
   g.Sy = round_half_up(H, translation_ratio); g.Sx = round_half_up(W, translation_ratio);
   g.cy = round_half_up(H, cutout_ratio); g.cx = round_half_up(W, cutout_ratio);
-  const bool color = (ops_mask & OP_COLOR) != 0;
+  const LaunchPlan p = plan_for(n, E, ops_mask);
   bg::Launch L(stream, adj ? "diffaug_adjoint" : "diffaug", 0, 8.0 * n * E + 32.0 * n);
-  const unsigned gx = (unsigned)std::min(n, kMaxBlocks);
-  const dim3 block(color && E >= (size_t)kBigFloats ? kTBig : kTSmall);
-  const size_t red_bytes = kMaxWaves * sizeof(float);
-  // (without colour there is no mean to wait for: every sample size is one gathering sweep straight from memory)
-  if (resident(E) && color) {
-    // the image's room: the sample, the alignment pad in front of it, rounded up to whole float4s
-    const size_t lds = red_bytes + (E + 3 + 3) / 4 * 16;
-    if (adj) bg::launch(diffaug_kernel<true, true>, dim3(gx), block, lds, L.s, in, out, params, g);
-    else bg::launch(diffaug_kernel<false, true>, dim3(gx), block, lds, L.s, in, out, params, g);
+  const dim3 grid(p.gx, p.gy), block(p.threads);
+  if (p.resident) {
+    if (adj) bg::launch(diffaug_kernel<true, true>, grid, block, p.lds, L.s, in, out, params, g);
+    else bg::launch(diffaug_kernel<false, true>, grid, block, p.lds, L.s, in, out, params, g);
   } else {
-    // a small batch of large images is cut along the sample until the chip has two workgroups per compute unit: with colour every
-    // workgroup of a sample repeats sweep 1, so no further.  Without colour a cut costs nothing: 256-thread workgroups, eight per
-    // compute unit, at least a quarter of a chunk each
-    const unsigned want = color ? 512u : 2048u;
-    unsigned gy = (unsigned)std::min<size_t>(std::max<size_t>(E / (color ? kChunkFloats : kChunkFloats / 4), 1), 64);
-    gy = std::min(gy, std::max(1u, want / gx));
-    if (adj) bg::launch(diffaug_kernel<true, false>, dim3(gx, gy), block, red_bytes, L.s, in, out, params, g);
-    else bg::launch(diffaug_kernel<false, false>, dim3(gx, gy), block, red_bytes, L.s, in, out, params, g);
+    if (adj) bg::launch(diffaug_kernel<true, false>, grid, block, p.lds, L.s, in, out, params, g);
+    else bg::launch(diffaug_kernel<false, false>, grid, block, p.lds, L.s, in, out, params, g);
   }
   return L.done("diffaug_kernel");
 }
@@ -287,6 +303,19 @@ int bg_diffaug_route(int H, int W, int C, int* is_resident, int* resident_floats
   BG_REQUIRE(H > 0 && W > 0 && C > 0, BG_ERR_BAD_SHAPE, "bg_diffaug_route: H=%d W=%d C=%d", H, W, C);
   if (is_resident) *is_resident = resident((size_t)H * W * C) ? 1 : 0;
   if (resident_floats) *resident_floats = kResident;
+  return BG_OK;
+}
+
+int bg_diffaug_plan(int n, int H, int W, int C, int ops_mask, int* is_resident, int* threads, int* grid_x, int* grid_y, int* lds_bytes) {
+  BG_REQUIRE(n > 0 && H > 0 && W > 0 && C > 0 && (size_t)H * W * C <= (size_t)1 << 30, BG_ERR_BAD_SHAPE, "bg_diffaug_plan: n=%d H=%d W=%d C=%d", n, H,
+             W, C);
+  BG_REQUIRE(ops_mask >= 0 && ops_mask <= 7, BG_ERR_UNSUPPORTED, "bg_diffaug_plan: ops_mask=%d (bits: 1 color, 2 translation, 4 cutout)", ops_mask);
+  const LaunchPlan p = plan_for(n, (size_t)H * W * C, ops_mask);
+  if (is_resident) *is_resident = p.resident ? 1 : 0;
+  if (threads) *threads = (int)p.threads;
+  if (grid_x) *grid_x = (int)p.gx;
+  if (grid_y) *grid_y = (int)p.gy;
+  if (lds_bytes) *lds_bytes = (int)p.lds;
   return BG_OK;
 }
 

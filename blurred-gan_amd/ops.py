@@ -430,6 +430,14 @@ class diffaug:
         return dict(resident=bool(r.value), resident_floats=f.value)
 
     @staticmethod
+    def plan(n, H, W, Cc, ops_mask=7):
+        """What fwd / adjoint launch for this batch and mask: dict(resident, threads, grid_x, grid_y, lds_bytes) (host only)."""
+        names = ("resident", "threads", "grid_x", "grid_y", "lds_bytes")
+        v = [C.c_int() for _ in names]
+        check(_lib.load().bg_diffaug_plan(int(n), int(H), int(W), int(Cc), int(ops_mask), *[C.byref(x) for x in v]), "bg_diffaug_plan")
+        return dict(zip(names, [bool(v[0].value)] + [x.value for x in v[1:]]))
+
+    @staticmethod
     def decode(u, H, W, ops_mask=7, translation_ratio=0.125, cutout_ratio=0.5):
         """The library's own decode of one row of eight uniforms, on the host: dict(b, s, c, ty, tx, y0, x0, cy, cx, Sy, Sx)."""
         row = (C.c_float * 8)(*[float(v) for v in u])

@@ -309,8 +309,13 @@ int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float
  * (BG_ERR_UNSUPPORTED); ratios outside [0, 1] and unknown mask bits: BG_ERR_UNSUPPORTED.  A refused call launches nothing.  No
  * call takes a step-program binding: params live in device memory.
  * bg_diffaug_decode: the decode above on the host, for one row u[8]: bsc[3] = {b, s, c}, geo[8] = {ty, tx, oy - cy / 2,
- * ox - cx / 2, cy, cx, Sy, Sx}. */
+ * ox - cx / 2, cy, cx, Sy, Sx}.
+ * bg_diffaug_plan (host only): what bg_diffaug_f32 / bg_diffaug_adjoint_f32 launch for this batch and mask -- the calls take
+ * their geometry from the same function.  *resident = 1: the resident kernel (never without colour, whatever bg_diffaug_route says
+ * of the sample size); threads per workgroup; the grid (grid_x workgroups stride over the n samples, grid_y cut a sample's output on
+ * the two-sweep route, 1 on the resident one); the dynamic LDS in bytes.  Any out pointer may be NULL. */
 int bg_diffaug_route(int H, int W, int C, int* resident, int* resident_floats);
+int bg_diffaug_plan(int n, int H, int W, int C, int ops_mask, int* resident, int* threads, int* grid_x, int* grid_y, int* lds_bytes);
 int bg_diffaug_decode(const float* u, int H, int W, int ops_mask, float translation_ratio, float cutout_ratio, float* bsc, int* geo);
 int bg_diffaug_f32(const float* x, float* y, const float* params, int n, int H, int W, int C, int ops_mask, float translation_ratio,
                    float cutout_ratio, int linear, void* stream);
