@@ -84,6 +84,11 @@ SIGNATURES = {
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
     "bg_diffaug_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "bg_diffaug_adjoint_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "bg_mbstd_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "bg_mbstd_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "bg_mbstd_fwd_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _z, _p]),
+    "bg_mbstd_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "bg_mbstd_gp_f32": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _z, _p]),
     "bg_spectral_route":(_i, [_i, _i, _i] + [C.POINTER(_i)] * 8),
     "bg_spectral_workspace_bytes": (_z, [_p, _i]),
     "bg_spectral_power_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _z, _p]),
@@ -146,6 +151,7 @@ SIGNATURES = {
 }
 
 COMM_ID_BYTES = 128
+MBSTD_PLAN_INTS = 12           # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 LOSS_WASSERSTEIN, LOSS_HINGE, LOSS_NONSATURATING = 0, 1, 2      # include/bgan.h bg_gan_loss
 BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*

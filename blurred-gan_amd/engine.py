@@ -4,7 +4,8 @@ written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
 A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization] [+ LeakyReLU |
 tanh] [+ Dropout]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
-one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  Stage fusion on the device:
+one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  MinibatchStdDev is a stage of its
+own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent and source).  Stage fusion on the device:
   conv (+bias) + LeakyReLU + Dropout      -> one launch (epilogue of the MFMA kernel)
   dgrad + LeakyReLU'/Dropout' of the stage below -> one launch (BG_EPI_MUL_GRAD epilogue)
   pooling backward + LeakyReLU'/Dropout' of the stage below -> one launch (the upsample with ref / keep)
@@ -29,6 +30,8 @@ from .layers import SpectralNormalization
 
 
 RESAMPLE = ("upsample", "avgpool")
+PARAMETER_FREE = RESAMPLE + ("mbstd",)      # stages of their own without variables (layers.MinibatchStdDev: not linear, see mbstd_*)
+SOURCE_KINDS = ("ln", "mbstd")              # _gp_kinds: stages that are not piecewise linear and add a source term to the penalty
 
 
 class Stage:
@@ -79,6 +82,14 @@ class _StageBuffers:
             lst[i] = torch.empty((self.B,) + self._net.stages[i].out_shape, dtype=torch.float32, device=self._device)
         return lst[i]
 
+    def mbstd_source(self, i):
+        """(src, fdot) of MinibatchStdDev stage i: the penalty's source at the stage's primal input (kept in s[i]) and the groups'
+        tangent scalar."""
+        st = self._net.stages[i]
+        if self.s[i] is None:
+            self.s[i] = torch.empty((self.B,) + st.in_shape, dtype=torch.float32, device=self._device)
+        return self.s[i], self.mbstd_stats(i)[4]
+
 
 class Context(_StageBuffers):
     """Activation / gradient buffers of one pass at a fixed batch size (caller-owned HBM)."""
@@ -121,6 +132,7 @@ class Context(_StageBuffers):
         rates = {float(st.drop) for st in net.stages if st.drop}
         self.keep_rate = rates.pop() if len(rates) == 1 else None      # None: stages differ, draw per stage
         self._net, self._device = net, device
+        net.check_rows(B)
         self._extra = {}
         self._bn_grad_scratch = {}
         self.dropout_active = False
@@ -173,6 +185,18 @@ class Context(_StageBuffers):
             self._bn_grad_scratch[i] = tuple(torch.empty(C, dtype=torch.float32, device=self._device) for _ in range(2))
         return self._bn_grad_scratch[i]
 
+    def mbstd_stats(self, i):
+        """(mu, rs, f, q, fdot) of MinibatchStdDev stage i: the groups' column means and 1 / s the forward leaves, the groups'
+        statistic, the sum of the incoming gradient's new channel the backward leaves (the penalty's source reads it) and the
+        tangent's scalar."""
+        key = ("mbstd", i)
+        if key not in self._extra:
+            st = self._net.stages[i]
+            n, E = self.B // st.lin.group_size, int(np.prod(st.in_shape))
+            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self._device)
+            self._extra[key] = (f(n, E), f(n, E), f(n), f(n), f(n))
+        return self._extra[key]
+
     def keep_u(self, i, rows):
         """Room for u of LN stage i on samples ``rows`` = (lo, hi): what the first-order backward leaves for the penalty."""
         n = rows[1] - rows[0]
@@ -220,6 +244,12 @@ class _RowView(_StageBuffers):
         self.zdot = ctx._extra.setdefault(("rowview_zdot", lo, hi), [None] * len(ctx.a))
         self.s = ctx._extra.setdefault(("rowview_s", lo, hi), [None] * len(ctx.a))
 
+    def mbstd_stats(self, i):
+        """The groups of samples [lo, hi) out of the pass's (groups are consecutive and the slices whole multiples of a group)."""
+        G = self._net.stages[i].lin.group_size
+        assert self.lo % G == 0 and self.hi % G == 0, (self.lo, self.hi, G)
+        return tuple(t[self.lo // G:self.hi // G] for t in self._ctx.mbstd_stats(i))
+
 
 class _BackwardPass:
     """What one Net.backward call carries from stage to stage."""
@@ -259,13 +289,15 @@ class Net:
                 if idx != 0:
                     raise NotImplementedError("GaussianBlur2D is only supported as the first layer (blurred_gan.py:31-34)")
                 self.blur = l
-            elif k in ("dense", "conv", "convT") + RESAMPLE:
+            elif k in ("dense", "conv", "convT") + PARAMETER_FREE:
+                if k == "mbstd":
+                    self.mbstd_check_position(flat_layers, idx, cur)
                 cur = Stage(l, s)
                 self.stages.append(cur)
             elif k == "bn":
                 if cur is not None and cur.ln is not None:
                     raise NotImplementedError("LayerNormalization together with BatchNormalization in one stage is not supported")
-                if cur is None or cur.kind in RESAMPLE or cur.bn is not None or cur.act is not None or cur.drop:
+                if cur is None or cur.kind in PARAMETER_FREE or cur.bn is not None or cur.act is not None or cur.drop:
                     raise NotImplementedError("BatchNormalization must directly follow a linear layer")
                 cur.bn = l
             elif k == "layernorm":
@@ -278,11 +310,11 @@ class Net:
                                               "resampling layer)")
                 cur.ln = l
             elif k == "lrelu":
-                if cur is None or cur.kind in RESAMPLE or cur.act is not None or cur.drop:
+                if cur is None or cur.kind in PARAMETER_FREE or cur.act is not None or cur.drop:
                     raise NotImplementedError("LeakyReLU must follow a linear layer or its BatchNormalization")
                 cur.act, cur.alpha = "lrelu", l.alpha
             elif k == "dropout":
-                if cur is None or cur.kind in RESAMPLE or cur.drop or cur.bn is not None or cur.act != "lrelu":
+                if cur is None or cur.kind in PARAMETER_FREE or cur.drop or cur.bn is not None or cur.act != "lrelu":
                     raise NotImplementedError("Dropout is supported after conv + LeakyReLU (demo_celeba.py:99-121)")
                 cur.drop = l.rate
                 if cur.drop:
@@ -314,7 +346,12 @@ class Net:
             raise NotImplementedError(f"SpectralNormalization layers of one model must share power_iterations, got {sorted(rounds)}")
         self.spectral_rounds = rounds.pop() if rounds else 0
         self.has_ln = any(st.ln is not None for st in self.stages)
+        self.mbstd_layers = [st.lin for st in self.stages if st.kind == "mbstd"]
+        # a stage with a source term in the penalty (LayerNormalization, MinibatchStdDev): such a critic takes the separate
+        # second-order route, and its first-order backward keeps what the source needs
+        self.has_source = self.has_ln or bool(self.mbstd_layers)
         self._ctx = {}
+        self._rows_checked = set()
         self._ws = None
         self._taps_cache = {}
         self._taps_ring = {"i": 0, "bufs": [], "evs": []}     # pinned staging of the tap uploads (blur_taps)
@@ -469,6 +506,7 @@ class Net:
         for i, st in enumerate(self.stages):
             xin = ctx.xin[i] = x.view(ctx.B, *st.in_shape)
             x = ctx.a[i]
+            if st.kind == "mbstd": self.mbstd_forward(ctx, i, st, xin, x); continue      # noqa: E701,E702
             if st.kind in RESAMPLE:
                 self._resample(st, xin, x)
             else:
@@ -627,12 +665,12 @@ class Net:
         if need_dw:
             self.store.ensure_opt_state()
         p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active(),
-                          keep_u_rows if self.has_ln else None)
+                          keep_u_rows if self.has_source else None)
         g, g_is_dz = dout, False
         for i in range(len(self.stages) - 1, -1, -1):
             st = self.stages[i]
             prev = self.stages[i - 1] if i > 0 else None
-            has_dw = need_dw and st.kind not in RESAMPLE
+            has_dw = need_dw and st.kind not in PARAMETER_FREE
             dz = ctx.dz[i] = self._grad_through_activation(p, i, st, g.view(ctx.B, *st.out_shape), g_is_dz)
             # SyncBN with a BatchNorm stage below: the data gradient goes FIRST, the lower stage's backward statistics are
             # reduced and their all-reduce is put in flight, and only then this stage's filter gradient runs -- the small
@@ -757,6 +795,7 @@ class Net:
         Returns (it, whether it is already that stage's dz: LeakyReLU' / Dropout' of a conv + LeakyReLU stage below ride in
         the data gradient's epilogue or in the pooling backward)."""
         ctx = p.ctx
+        if st.kind == "mbstd": return self.mbstd_backward(p, i, st, prev, dz)      # noqa: E701
         fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
         # the gradient at an LN stage's output lands in that stage's dz buffer and is turned into dz in place -- except where a row
         # exceeds what a wave holds in registers (ops.layernorm.route: chunks > 1), where the kernel wants a buffer of its own
@@ -813,6 +852,7 @@ class Net:
         kinds = []
         for i, st in enumerate(self.stages):
             last = i == len(self.stages) - 1
+            if st.kind == "mbstd": kinds.append("mbstd"); continue      # noqa: E701,E702  (its place in the network: mbstd_check_position)
             if st.kind == "conv" and st.bn is None and st.act == "lrelu" and not last:
                 kinds.append("conv" if st.ln is None else "ln")
             elif st.kind == "dense" and last and st.out_shape == (1,) and st.bn is None and st.act is None:
@@ -854,7 +894,7 @@ class Net:
         Not with LayerNormalization stages: their source backward (gp_ln_source_backward) needs the x-hat rows of the activations
         this pass overwrites, so such a critic takes ``gp_second_order`` on ``ctx.rows(lo, hi)``."""
         kinds = self._gp_kinds()
-        if "ln" in kinds: raise NotImplementedError("gp_second_order_merged overwrites activations the LayerNormalization source backward needs")  # noqa: E701
+        if set(kinds) & set(SOURCE_KINDS): raise NotImplementedError("gp_second_order_merged overwrites activations the LayerNormalization / MinibatchStdDev source backward needs")  # noqa: E701
         self.store.ensure_opt_state()
         for i, (kind, st) in enumerate(zip(kinds, self.stages)):
             xin = ctx.xin[i]                # [3B, ...]: activations of [fakes; reals], delta-bar_{i-1} in the x-hat rows
@@ -873,12 +913,12 @@ class Net:
         last contribution to every layer up to the top-most such stage, so those layers' slices go to the reducer from there."""
         kinds = self._gp_kinds()
         self.store.ensure_opt_state()
-        top = max((i for i, k in enumerate(kinds) if k == "ln"), default=-1)
+        top = max((i for i, k in enumerate(kinds) if k in SOURCE_KINDS), default=-1)
         v = v0
         for i, (kind, st) in enumerate(zip(kinds, self.stages)):
             vin = v.view(ctx.B, *st.in_shape)
             v = None if kind == "dense" else ctx.buf(ctx.v, i)
-            stage = self._gp_stage if kind != "ln" else functools.partial(self.gp_ln_stage, ctx, i)
+            stage = self._gp_stage if kind not in SOURCE_KINDS else functools.partial(getattr(self, f"gp_{kind}_stage"), ctx, i)
             stage(kind, st, vin, ctx.dz[i], 1.0, vin, ctx.a[i], v, reducer if i > top else None)
         self.gp_ln_source_backward(ctx, top, reducer)
 
@@ -904,6 +944,11 @@ class Net:
         stages' gamma / beta gradients, all accumulated into store.grad (beta = 1).  The tangent buffers ctx.v are dead by now and
         carry the gradient down.  Each layer's slice goes to the reducer behind the last launch that writes into it."""
         lam = None if top < 0 else ctx.s[top]
+        if top >= 0 and self.stages[top].kind == "mbstd":
+            # a MinibatchStdDev stage's source is a gradient at its primal INPUT, the output of the stage below: through that
+            # stage's activation (and its own source), then down from there
+            top -= 1
+            lam = self.gp_source_below(ctx, top, lam, False)
         for i in range(top, -1, -1):
             st, prev = self.stages[i], self.stages[i - 1] if i > 0 else None
             if st.kind not in RESAMPLE:
@@ -926,14 +971,70 @@ class Net:
                 self._conv(st, lam, tgt, True, EPI_MUL_GRAD, ref=ctx.a[i - 1], alpha=prev.alpha)
             else:
                 self._conv(st, lam, tgt, True, EPI_NONE)
-            lam = tgt
-            if prev.ln is not None:
-                # LeakyReLU' and the LayerNormalization backward of the stage below, plus its own source term
-                args = self.ln_args(ctx, i - 1, prev)
-                # in place where the kernel allows it, else into the stage's tangent buffer, dead since its source was taken
-                out = tgt if ops.layernorm.route(args["Cc"])["chunks"] == 1 else ctx.zdot[i - 1]
-                lam = ops.layernorm.bwd(tgt, ctx.z[i - 1], out, **args, beta=prev.ln.vars["beta"], lrelu_alpha=prev.alpha,
-                                        addend=ctx.s[i - 1], dgamma=self.store.grad_of(prev.ln, "gamma"), dbeta=self.store.grad_of(prev.ln, "beta"),
-                                        acc_beta=1.0, acc_scale=1.0, ws=self.workspace(ops.layernorm.workspace_bytes(args["R"], args["Cc"])))
-            elif prev.kind not in RESAMPLE and not fuse:      # conv + LeakyReLU below an UpSampling2D: no launch to fuse it into
-                ops.mul_grad(tgt, ctx.a[i - 1], tgt, alpha=prev.alpha)
+            lam = self.gp_source_below(ctx, i - 1, tgt, fuse)
+
+    def gp_source_below(self, ctx, j, tgt, fused):
+        """The source backward through stage j's activation: ``tgt`` is the gradient at its output (``fused``: LeakyReLU' is in it
+        already); returns the gradient at its linear op's output, with the stage's own source term where it has one."""
+        prev = self.stages[j]
+        if prev.ln is not None:
+            # LeakyReLU' and the LayerNormalization backward of the stage, plus its own source term
+            args = self.ln_args(ctx, j, prev)
+            # in place where the kernel allows it, else into the stage's tangent buffer, dead since its source was taken
+            out = tgt if ops.layernorm.route(args["Cc"])["chunks"] == 1 else ctx.zdot[j]
+            return ops.layernorm.bwd(tgt, ctx.z[j], out, **args, beta=prev.ln.vars["beta"], lrelu_alpha=prev.alpha,
+                                     addend=ctx.s[j], dgamma=self.store.grad_of(prev.ln, "gamma"), dbeta=self.store.grad_of(prev.ln, "beta"),
+                                     acc_beta=1.0, acc_scale=1.0, ws=self.workspace(ops.layernorm.workspace_bytes(args["R"], args["Cc"])))
+        if prev.kind not in RESAMPLE and not fused:      # conv + LeakyReLU below an UpSampling2D (or a MinibatchStdDev): no launch to fuse it into
+            ops.mul_grad(tgt, ctx.a[j], tgt, alpha=prev.alpha)
+        return tgt
+
+    # ---- MinibatchStdDev (DESIGN.md §5 "Minibatch standard deviation").  Public names for the reason the LayerNormalization helpers
+    # carry them: no configuration of the engine-trace fixture has the layer; tests/test_mbstd_cpu.py records what these enqueue.
+    def check_rows(self, rows):
+        """A pass (or a slice of one) of ``rows`` samples must hold whole groups of every MinibatchStdDev layer; checked once per
+        size, on the host."""
+        if self.mbstd_layers and rows not in self._rows_checked:
+            for l in self.mbstd_layers:
+                l.check_rows(rows)
+            self._rows_checked.add(rows)
+
+    @staticmethod
+    def mbstd_check_position(flat_layers, idx, cur):
+        """The layer stands directly before the critic's Flatten -> Dense(1), behind the last conv stage's LeakyReLU / Dropout /
+        AveragePooling2D; anywhere else (a generator included) it is refused."""
+        tail = [l for l, _ in flat_layers[idx + 1:]]
+        head = (len(tail) == 2 and tail[0].kind == "flatten" and tail[1].kind == "dense" and tail[1].units == 1
+                and getattr(tail[1], "activation", None) is None)
+        below = cur is not None and (cur.kind == "avgpool" or (cur.kind == "conv" and cur.bn is None and cur.act == "lrelu"))
+        if not (head and below):
+            raise NotImplementedError("MinibatchStdDev is supported directly before the critic's Flatten -> Dense(1) only, behind the last "
+                                      "conv stage's LeakyReLU / Dropout / AveragePooling2D (not in a generator, not in front of a conv)")
+
+    def mbstd_args(self, ctx, i, st):
+        nb = ops.mbstd.workspace_bytes(ctx.B, st.lin.group_size, st.ln_pixels, st.in_shape[-1])
+        return dict(G=st.lin.group_size, eps=st.lin.epsilon, ws=self.workspace(nb) if nb else None)
+
+    def mbstd_forward(self, ctx, i, st, xin, out):
+        """out = xin with the groups' statistic as one more channel; the groups' mu and 1 / s stay in ctx.mbstd_stats(i)."""
+        mu, rs, f = ctx.mbstd_stats(i)[:3]
+        return ops.mbstd.fwd(xin, out, mu, rs, f, **self.mbstd_args(ctx, i, st))
+
+    def mbstd_backward(self, p, i, st, prev, dz):
+        """_input_grad of a MinibatchStdDev stage: the gradient at its input into the buffer the stage below reads its output
+        gradient from (that stage's LeakyReLU' / Dropout' follow in its own launch); the groups' q stays for the penalty's source."""
+        ctx = p.ctx
+        below = ctx.gin if prev.ln is not None and ops.layernorm.route(prev.out_shape[-1])["chunks"] > 1 else ctx.dz
+        tgt = ctx.buf(below, i - 1).view(ctx.B, *st.in_shape)
+        mu, rs, _, q = ctx.mbstd_stats(i)[:4]
+        ops.mbstd.bwd(dz.view(ctx.B, *st.out_shape), ctx.xin[i], mu, rs, tgt, q, st.lin.group_size)
+        return tgt, False
+
+    def gp_mbstd_stage(self, ctx, i, kind, st, wx, wdz, wbeta, v, ref, vout, reducer):
+        """_gp_stage for a MinibatchStdDev stage, one launch: the tangent vout (v with the groups' fdot as the new channel) and the
+        source (kept in ctx.s[i]): the derivative of <v, J(x)^T u> w.r.t. the stage's primal input, u the first-order gradient the
+        backward of these rows saw (its q).  Nothing to hand to the reducer: the stage has no variables."""
+        assert reducer is None
+        mu, rs, _, q = ctx.mbstd_stats(i)[:4]
+        src, fdot = ctx.mbstd_source(i)
+        ops.mbstd.gp(v, ctx.xin[i], mu, rs, q, vout, src, fdot, **self.mbstd_args(ctx, i, st))

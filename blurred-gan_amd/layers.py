@@ -291,6 +291,41 @@ class AveragePooling2D(Layer):
         return (s[0] // 2, s[1] // 2, s[2])
 
 
+class MinibatchStdDev(Layer):
+    """The minibatch standard deviation layer of ProGAN / StyleGAN / StyleGAN2 (``num_new_features = 1``) at the top of a critic:
+    [N, H, W, C] -> [N, H, W, C + 1].  Samples are split into groups of ``group_size`` CONSECUTIVE samples (group g is rows
+    [g G, (g + 1) G)); per group and column (pixel, channel) s = sqrt(var_n x + epsilon) with the biased variance over the members,
+    f_g = the mean of s over all columns, and f_g becomes channel C of every pixel of every sample of the group.  No variables.
+
+    StyleGAN2 takes its groups strided (n, n + M, ...).  Here they are consecutive: the critic step runs [fakes; reals; x-hat] as one
+    pass and a group must not straddle two slices, data-parallel shards are contiguous, and the samples are i.i.d., so the statistic
+    has the same distribution.  Every pass of a step has B, 2B or 3B rows: the batch size must be a multiple of ``group_size``
+    (ValueError otherwise; the group is never shrunk).  The layer stands directly before the critic's Flatten -> Dense(1)."""
+    kind = "mbstd"
+
+    def __init__(self, group_size=4, epsilon=1e-8, num_new_features=1, **kw):
+        super().__init__(**kw)
+        if int(num_new_features) != 1:
+            raise NotImplementedError(f"MinibatchStdDev num_new_features={num_new_features!r}: only one new feature is supported")
+        if int(group_size) < 2:
+            raise ValueError(f"MinibatchStdDev group_size={group_size!r}: a group needs at least 2 samples")
+        if not float(epsilon) > 0.0:
+            raise ValueError(f"MinibatchStdDev epsilon={epsilon!r}: must be positive")
+        self.group_size, self.epsilon, self.num_new_features = int(group_size), float(epsilon), 1
+
+    def out_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"MinibatchStdDev needs an [H, W, C] map, got {tuple(s)}")
+        return (s[0], s[1], s[2] + 1)
+
+    def check_rows(self, rows):
+        """``rows``: the samples per slice of a pass.  Groups are consecutive and never straddle the slices of a step's passes."""
+        if int(rows) % self.group_size:
+            raise ValueError(f"MinibatchStdDev(group_size={self.group_size}): a pass of {rows} rows per slice is no multiple of the group "
+                             f"size.  Every pass of a step has B, 2B or 3B rows, so the (per-device) batch size B must satisfy "
+                             f"B % group_size == 0; the group is not shrunk")
+
+
 class Reshape(Layer):
     kind = "reshape"
 

@@ -15,6 +15,10 @@ The critic takes ``normalization="layer"``: a LayerNormalization over the channe
 WGAN-GP paper's critic; BatchNormalization cannot stand there, the penalty is defined per sample).  Map sizes are unchanged, every
 block gains 2 * C variables; it combines with ``downsampling="pool"``.
 
+``minibatch_stddev=G`` puts a ``layers.MinibatchStdDev(group_size=G)`` in front of the critic's Flatten: one more feature map, the
+Dense kernel becomes [P * (C + 1), 1] (flattened in (H, W, C + 1) order); the batch size must be a multiple of G.  It combines with
+``downsampling="pool"``, ``normalization="layer"`` and ``spectral_norm=True``.
+
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
 engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``."""
 from __future__ import annotations
@@ -70,14 +74,18 @@ class DCGANGenerator(layers.SpectralSequential):
 
 
 class DCGANDiscriminator(layers.SpectralSequential):
-    def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, spectral_norm=False, **kwargs):
+    def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, spectral_norm=False, minibatch_stddev=None,
+                 **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm = bool(spectral_norm)
         if downsampling not in ("stride", "pool"):
             raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
         if normalization not in (None, "layer"):
             raise ValueError(f"normalization must be None or 'layer', got {normalization!r}")
+        if minibatch_stddev is not None and (isinstance(minibatch_stddev, bool) or int(minibatch_stddev) != minibatch_stddev):
+            raise ValueError(f"minibatch_stddev must be None or a group size, got {minibatch_stddev!r}")
         self.downsampling, self.normalization = downsampling, normalization
+        self.minibatch_stddev = None if minibatch_stddev is None else int(minibatch_stddev)
         pool = downsampling == "pool"
         for i, c in enumerate(_D[arch]):
             kw = dict(input_shape=list(IMAGE_SHAPE[arch])) if i == 0 else {}
@@ -88,5 +96,7 @@ class DCGANDiscriminator(layers.SpectralSequential):
             self.add(layers.Dropout(0.3))
             if pool:
                 self.add(layers.AveragePooling2D())
+        if self.minibatch_stddev is not None:
+            self.add(layers.MinibatchStdDev(group_size=self.minibatch_stddev))
         self.add(layers.Flatten())
         self.add(layers.Dense(1, activation="linear"))

@@ -468,6 +468,68 @@ class diffaug:
         return dx
 
 
+# ------------------------------------------------------------------ minibatch standard deviation (include/bgan.h)
+class mbstd:
+    """The MinibatchStdDev kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's public
+    functions by name; these calls are recorded by the minibatch standard deviation tests' own recorder."""
+    CALLS = {"fwd": 0, "bwd": 1, "gp": 2}
+    PLAN = ("resident", "threads", "grid_x", "grid_y", "grid_y_emit", "lds_bytes", "launches", "vecs", "trips_min", "trips_max", "head", "tail")
+
+    @staticmethod
+    def plan(N, G, P, Cc, call="fwd", offset_floats=0):
+        """What ``call`` ('fwd', 'bwd', 'gp') launches for N samples in groups of G (host only): dict over mbstd.PLAN."""
+        out = (C.c_int * _lib.MBSTD_PLAN_INTS)()
+        check(_lib.load().bg_mbstd_plan(int(N), int(G), int(P), int(Cc), mbstd.CALLS[call], int(offset_floats), out), "bg_mbstd_plan")
+        return dict(zip(mbstd.PLAN, [bool(out[0])] + list(out)[1:]))
+
+    @staticmethod
+    def workspace_bytes(N, G, P, Cc):
+        return _lib.load().bg_mbstd_workspace_bytes(int(N), int(G), int(P), int(Cc))
+
+    @staticmethod
+    def _ws_bytes(ws):
+        return 0 if ws is None else ws.numel() * ws.element_size()
+
+    @staticmethod
+    def _geo(x, y, G, *stats):
+        """(N, P, C) of x [N, ..., C] against y [N, ..., C + 1] and the per-group buffers."""
+        N, Cc = int(x.shape[0]), int(x.shape[-1])
+        P = x.numel() // max(N * Cc, 1)
+        assert y.numel() == N * P * (Cc + 1), (tuple(x.shape), tuple(y.shape))
+        for t in stats:
+            assert t.numel() >= (N // G) * P * Cc
+        return N, P, Cc
+
+    @staticmethod
+    def fwd(x, y, mu, rs, f, G, eps=1e-8, ws=None):
+        """y [N, ..., C + 1] = x with the group's mean standard deviation as channel C; keeps mu, rs = 1 / s per group and column, f
+        per group (bg_mbstd_fwd_f32)."""
+        _f32(x, y, mu, rs, f, ws)
+        N, P, Cc = mbstd._geo(x, y, G, mu, rs)
+        check(_lib.load().bg_mbstd_fwd_f32(_ptr(x), _ptr(y), _ptr(mu), _ptr(rs), _ptr(f), N, int(G), P, Cc, eps, _ptr(ws), mbstd._ws_bytes(ws),
+                                           _stream()), "bg_mbstd_fwd_f32")
+        return y
+
+    @staticmethod
+    def bwd(u, x, mu, rs, dx, q, G):
+        """dx = u[..., :C] + q * k * (x - mu) * rs with q = the group's sum of u[..., C], kept in ``q`` (bg_mbstd_bwd_f32)."""
+        _f32(u, x, mu, rs, dx, q)
+        N, P, Cc = mbstd._geo(x, u, G, mu, rs)
+        assert dx.numel() == x.numel() and q.numel() >= N // G
+        check(_lib.load().bg_mbstd_bwd_f32(_ptr(u), _ptr(x), _ptr(mu), _ptr(rs), _ptr(dx), _ptr(q), N, int(G), P, Cc, _stream()), "bg_mbstd_bwd_f32")
+        return dx
+
+    @staticmethod
+    def gp(d, x, mu, rs, q, vout, src, fdot, G, eps=1e-8, ws=None):
+        """The penalty's tangent vout (d with fdot as channel C) and source src at the layer's primal input (bg_mbstd_gp_f32)."""
+        _f32(d, x, mu, rs, q, vout, src, fdot, ws)
+        N, P, Cc = mbstd._geo(x, vout, G, mu, rs)
+        assert d.numel() == x.numel() == src.numel() and q.numel() >= N // G and fdot.numel() >= N // G
+        check(_lib.load().bg_mbstd_gp_f32(_ptr(d), _ptr(x), _ptr(mu), _ptr(rs), _ptr(q), _ptr(vout), _ptr(src), _ptr(fdot), N, int(G), P, Cc, eps,
+                                          _ptr(ws), mbstd._ws_bytes(ws), _stream()), "bg_mbstd_gp_f32")
+        return vout
+
+
 # ------------------------------------------------------------------ spectral normalisation (include/bgan.h "spectral normalisation")
 class SpectralTable:
     """The descriptor table of one batch of wrapped layers: the rows in host memory (the calls check them before anything touches

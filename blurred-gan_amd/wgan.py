@@ -466,6 +466,7 @@ class WGAN:
         self.batch_size = B
         hp = self.hparams
         G, D = self.generator.net(), self.discriminator.net()
+        D.check_rows(B)             # MinibatchStdDev: the slices of every pass of this step hold whole groups
         D.spectral_update()         # a spectrally normalised critic: its power round, before any forward of this step
         z = self._inj("z_d")
         z = self._as_device(z) if z is not None else self._uniform("z_d", (B, self.latent_size))
@@ -505,9 +506,9 @@ class WGAN:
             ds3 = self._buf("ds3", (3 * B,))
             ops.fill(ds3[2 * B:], 1.0)
             self._d_loss(fs, rs, None, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)      # seeds only; metrics below
-            # a critic with LayerNormalization stages takes the separate second-order route whatever the switch says: the merged one
+            # a critic with LayerNormalization stages (or a MinibatchStdDev: any stage with a source term) takes the separate second-order route whatever the switch says: the merged one
             # overwrites the x-hat rows of the activations that the stages' source backward reads (engine.gp_second_order_merged)
-            one_wgrad = self.merge_gp_filter_gradients and not D.has_ln
+            one_wgrad = self.merge_gp_filter_gradients and not D.has_source
             g = D.backward(c3, ds3.view(3 * B, 1), need_dx=True, need_dw=True, beta=0.0, scale=1.0, dw_rows=2 * B,
                            dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad, keep_u_rows=(2 * B, 3 * B))
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))

@@ -63,7 +63,7 @@ class DCGANGenerator(layers.SpectralSequential):
 class DCGANDiscriminator(layers.SpectralSequential):
     """demo_mnist.py:74-86."""
 
-    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, minibatch_stddev=0, **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm = bool(spectral_norm)
         pool = {"stride": False, "pool": True}[downsampling]
@@ -83,6 +83,8 @@ class DCGANDiscriminator(layers.SpectralSequential):
         self.add(layers.Dropout(0.3))
         if pool:
             self.add(layers.AveragePooling2D())
+        if minibatch_stddev:
+            self.add(layers.MinibatchStdDev(group_size=minibatch_stddev))
         self.add(layers.Flatten())
         self.add(layers.Dense(1))
 
@@ -109,6 +111,9 @@ def make_parser():
     parser.add_argument("--critic-spectral-norm", dest="critic_spectral_norm", action="store_true",
                         help="spectral normalisation (Miyato et al. 2018) of every Conv2D and Dense of the critic: the step computes "
                              "with W / sigma, one power round per critic step")
+    parser.add_argument("--critic-mbstd", dest="critic_mbstd", type=int, default=0, metavar="G",
+                        help="minibatch standard deviation layer in front of the critic's head, over groups of G consecutive samples "
+                             "(0: off; the batch size must be a multiple of G)")
     parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
                         help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
                              "the generator average)")
@@ -172,7 +177,8 @@ def main(argv=None):
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
     gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm)
-    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm)
+    disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
+                              minibatch_stddev=args.critic_mbstd)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

@@ -322,6 +322,46 @@ int bg_diffaug_f32(const float* x, float* y, const float* params, int n, int H, 
 int bg_diffaug_adjoint_f32(const float* dy, float* dx, const float* params, int n, int H, int W, int C, int ops_mask,
                            float translation_ratio, float cutout_ratio, void* stream);
 
+/* ---- minibatch standard deviation (Karras et al. 2018; StyleGAN2's layer with one new feature; layers.MinibatchStdDev) ---------
+ * x: [N, P, C] fp32, P pixels; a group is G CONSECUTIVE samples (N % G == 0, G >= 2: BG_ERR_BAD_SHAPE otherwise).  Per group g and
+ * column (p, c), with k = 1 / (G * P * C):
+ *   mu = mean_n x,   s = sqrt(mean_n (x - mu)^2 + eps)   (two-pass, centred),   f_g = mean_{p,c} s.
+ * bg_mbstd_fwd_f32: y [N, P, C + 1] = x in channels [0, C), f_g in channel C of every pixel of every sample of the group; keeps
+ * mu and rs = 1 / s ([N / G, P * C] each) and f ([N / G]) for the other calls.
+ * bg_mbstd_bwd_f32: u is the gradient at y; q_g = sum_{n in g, p} u[n, p, C] (kept in q [N / G]: the penalty's source needs it),
+ *   dx = u[..., :C] + q_g * k * (x - mu) * rs.
+ * bg_mbstd_gp_f32: the gradient penalty's tangent and source in one call, d the tangent at x, q from the first-order backward:
+ *   vout [N, P, C + 1] = d in channels [0, C),  fdot_g = k * sum_{n in g, p, c} (x - mu) * rs * d  in channel C  (kept in fdot [N / G]);
+ *   src = q_g * k * rs^3 * ((d - dbar) * eps + [(d - dbar) * var - (x - mu) * m]),  dbar = mean_n d,  m = mean_n (x - mu) * d,
+ *   which is q_g * k * ((d - dbar) / s - (x - mu) * m / s^3) with the difference taken before the division.  At G = 2 the bracket is
+ *   identically zero (the members' centred values are one another's negatives) and is not evaluated.
+ * mu is formed as x_0 + mean_n (x_n - x_0) and f_g as s_0 + mean (s - s_0) over the columns: equal members give mu = x_0, equal
+ * columns f_g = s_0, exactly and in any order of summation (a group without variance: f_g = sqrt(eps)).
+ * A column whose members are all equal has x - mu = 0 exactly and adds exactly 0 to dx and fdot (and to src where d is equal too).
+ * Every sum runs in a fixed order: per-thread partials in loop order, a fixed tree, no atomics -- the same bits on every run.
+ * A group of at most 15356 floats is read from memory once (one workgroup per group, the group in LDS between its statistics and
+ * its output; one launch).  A larger group takes two launches in the forward and the penalty call: its columns cut over several
+ * workgroups that leave partial sums in the workspace (bg_mbstd_workspace_bytes; 0 on the resident route), then the output, every
+ * workgroup adding the partials in index order.  The backward is one launch on either route and takes no workspace.
+ * Pointers 4-byte aligned (BG_ERR_BAD_ALIGNMENT); 16 bytes per lane wherever an address allows, scalar heads and tails elsewhere
+ * (the output's row stride C + 1 is odd for every stock critic: its groups are swept as flat ranges).  NULL: BG_ERR_NULL; a pointer
+ * the runtime knows as host memory: BG_ERR_UNSUPPORTED.  No output may alias an input.  A refused call launches nothing.  No call
+ * takes a step-program binding.
+ * bg_mbstd_plan (host only): what call (0 forward, 1 backward, 2 penalty) launches, the calls take their geometry from the same
+ * function.  offset_floats in [0, 4): where the swept pointer (mu; the backward: dx) stands after a 16-byte boundary.
+ * out[BG_MBSTD_PLAN_INTS] = {resident, threads, grid_x (workgroups stride over the groups), grid_y of the column phase (the
+ * backward: of its one sweep), grid_y of the output phase, dynamic LDS bytes, launches, float4s of that sweep per group, fewest and
+ * most float4 trips of a lane, scalar head, scalar tail}. */
+#define BG_MBSTD_PLAN_INTS 12
+int bg_mbstd_plan(int N, int G, int P, int C, int call, int offset_floats, int* out);
+size_t bg_mbstd_workspace_bytes(int N, int G, int P, int C);
+int bg_mbstd_fwd_f32(const float* x, float* y, float* mu, float* rs, float* f, int N, int G, int P, int C, float eps, void* ws_d,
+                     size_t ws_bytes, void* stream);
+int bg_mbstd_bwd_f32(const float* u, const float* x, const float* mu, const float* rs, float* dx, float* q, int N, int G, int P, int C,
+                     void* stream);
+int bg_mbstd_gp_f32(const float* d, const float* x, const float* mu, const float* rs, const float* q, float* vout, float* src,
+                    float* fdot, int N, int G, int P, int C, float eps, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---- spectral normalisation (Miyato et al. 2018; layers.SpectralNormalization) -------------------------------------------
  * A wrapped layer's kernel is the row-major matrix W[K, N] (N = the kernel's last axis, K = the rest); the engine runs on
  * W-bar = W / sigma, sigma from a running power iteration with the unit vectors u[N], v[K] (layer state).
