@@ -79,6 +79,9 @@ SIGNATURES = {
     "bg_ln_bwd_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p, _f, _z, _p, _p, _i, _i, _p, _p, _i, _f, _f, _p, _z, _p]),
     "bg_ln_tangent_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _p]),
     "bg_ln_gp_source_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _f, _f, _p, _z, _p]),
+    "bg_pixelnorm_route": (_i, [_i, C.POINTER(_i)]),
+    "bg_pixelnorm_fwd_f32": (_i, [_p, _p, _p, _i, _i, _f, _f, _p]),
+    "bg_pixelnorm_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "bg_diffaug_plan": (_i, [_i, _i, _i, _i, _i] + [C.POINTER(_i)] * 5),
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
@@ -151,7 +154,8 @@ SIGNATURES = {
 }
 
 COMM_ID_BYTES = 128
-MBSTD_PLAN_INTS = 12           # include/bgan.h BG_MBSTD_PLAN_INTS
+PIXELNORM_ROUTE_INTS = 8       # include/bgan.h BG_PIXELNORM_ROUTE_INTS
+MBSTD_PLAN_INTS = 12          # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 LOSS_WASSERSTEIN, LOSS_HINGE, LOSS_NONSATURATING = 0, 1, 2      # include/bgan.h bg_gan_loss
 BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*

@@ -3,7 +3,7 @@ gradient-penalty linearised forward on the HIP kernels.  There is no tape: every
 written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
 A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization] [+ LeakyReLU |
-tanh] [+ Dropout]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
+tanh] [+ Dropout | PixelNormalization]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
 one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  MinibatchStdDev is a stage of its
 own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent and source).  Stage fusion on the device:
   conv (+bias) + LeakyReLU + Dropout      -> one launch (epilogue of the MFMA kernel)
@@ -11,6 +11,8 @@ own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent
   pooling backward + LeakyReLU'/Dropout' of the stage below -> one launch (the upsample with ref / keep)
   BatchNormalization + LeakyReLU          -> stats pass + one apply pass
   LayerNormalization + LeakyReLU + Dropout -> one pass over the conv's stored output (per-pixel statistics, csrc/layernorm.hip)
+  LeakyReLU + PixelNormalization          -> one pass over the linear op's stored output (csrc/pixelnorm.hip); a PixelNormalization
+                                             that is the network's first layer normalises the latents, one launch, no backward
 
 Net.forward and Net.backward are input / pass set-up, a loop over the stages, and one helper per concern (DESIGN.md §5
 "Engine map"); tests/test_engine_trace_cpu.py holds the order and the arguments of everything they enqueue.
@@ -42,6 +44,8 @@ class Stage:
         self.out_shape = tuple(lin.out_shape(in_shape))
         self.bn = None
         self.ln = None              # layers.LayerNormalization between a Conv2D and its LeakyReLU (the critic's normalisation)
+        self.pn = None              # layers.PixelNormalization directly behind the stage's LeakyReLU (the generator's normalisation)
+        self.pn_channels = None     # the C it normalises over: the last axis of the map at the layer (a Dense's, behind its Reshape)
         self.act = getattr(lin, "activation", None)
         self.alpha = 1.0
         self.drop = None
@@ -59,7 +63,7 @@ class Stage:
 
     @property
     def fusable_grad(self):
-        return self.bn is None and self.ln is None and self.act == "lrelu"
+        return self.bn is None and self.ln is None and self.pn is None and self.act == "lrelu"
 
     @property
     def drop_scale(self):
@@ -74,6 +78,11 @@ class Stage:
     def ln_pixels(self):
         """Rows of an LN stage's [R, C] view per sample: its map's pixels."""
         return int(np.prod(self.out_shape[:-1]))
+
+    @property
+    def pn_rows(self):
+        """Rows of a PixelNormalization stage's [R, C] view per sample."""
+        return int(np.prod(self.out_shape)) // self.pn_channels
 
 
 class _StageBuffers:
@@ -112,10 +121,10 @@ class Context(_StageBuffers):
             self.a.append(f(B, *st.out_shape))
             self.dz.append(None)
             self.v.append(None)
-            self.z.append(f(B, *st.out_shape) if st.bn is not None or st.ln is not None else None)
-            c = B * st.ln_pixels if st.ln is not None else st.out_shape[-1]
+            self.z.append(f(B, *st.out_shape) if st.bn is not None or st.ln is not None or st.pn is not None else None)
+            c = B * st.ln_pixels if st.ln is not None else B * st.pn_rows if st.pn is not None else st.out_shape[-1]
             self.mean.append(f(c) if st.bn is not None or st.ln is not None else None)
-            self.inv.append(f(c) if st.bn is not None or st.ln is not None else None)
+            self.inv.append(f(c) if st.bn is not None or st.ln is not None or st.pn is not None else None)      # PixelNormalization: the rows' r
             self.keep.append(None)
         # dropout masks of all stages live in ONE uint8 buffer (16-byte aligned slices): a pass draws them with one launch
         DR = self.drop_rows
@@ -280,6 +289,7 @@ class Net:
         self.blur = None
         self.capture_branches = None     # test instrumentation (gp_second_order_merged): a list collects the x-hat rows' LeakyReLU signs
         self.stages: List[Stage] = []
+        self.latent_pn = None            # layers.PixelNormalization as the network's first layer: the latents' normalisation
         self.in_shape = tuple(flat_layers[0][1])
         cur = None
         n_masks = 0
@@ -292,8 +302,14 @@ class Net:
             elif k in ("dense", "conv", "convT") + PARAMETER_FREE:
                 if k == "mbstd":
                     self.mbstd_check_position(flat_layers, idx, cur)
+                    if cur.pn is not None:
+                        raise NotImplementedError(self.PN_RULE + " (MinibatchStdDev behind a PixelNormalization stage is not supported)")
                 cur = Stage(l, s)
                 self.stages.append(cur)
+            elif k == "pixelnorm":
+                self.pn_place(flat_layers, idx, cur)
+            elif k in ("bn", "layernorm", "dropout", "lrelu") and cur is not None and cur.pn is not None:
+                raise NotImplementedError(self.PN_RULE + f" (a {type(l).__name__} follows the PixelNormalization of its stage)")
             elif k == "bn":
                 if cur is not None and cur.ln is not None:
                     raise NotImplementedError("LayerNormalization together with BatchNormalization in one stage is not supported")
@@ -325,7 +341,7 @@ class Net:
                 raise NotImplementedError(f"layer kind {k!r}")
         for st in self.stages:
             st.folds_inference_bn = st.bn is not None and st.kind != "dense" and st.lin.vars.get("bias") is None
-            if st.kind == "dense" and st.bn is None and st.act is not None:
+            if st.kind == "dense" and st.bn is None and st.pn is None and st.act is not None:
                 raise NotImplementedError("Dense + activation without BatchNormalization is not on the reference path")
             if st.act == "tanh" and st.bn is not None:
                 raise NotImplementedError("tanh after BatchNormalization is not on the reference path")
@@ -350,6 +366,7 @@ class Net:
         # a stage with a source term in the penalty (LayerNormalization, MinibatchStdDev): such a critic takes the separate
         # second-order route, and its first-order backward keeps what the source needs
         self.has_source = self.has_ln or bool(self.mbstd_layers)
+        self.has_pn = self.latent_pn is not None or any(st.pn is not None for st in self.stages)
         self._ctx = {}
         self._rows_checked = set()
         self._ws = None
@@ -497,6 +514,7 @@ class Net:
         x = self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)
         ctx.aug = augment
         if augment is not None: x = self.aug_forward(ctx, x)      # noqa: E701
+        if self.latent_pn is not None: x = self.pn_latents(ctx, x)      # noqa: E701
         ctx.dropout_active = bool(training)
         # one launch draws the masks of all stages; where their rates differ, or masks are handed in, each stage sets its own
         one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
@@ -566,6 +584,7 @@ class Net:
         """Stage i's linear op with what its epilogue fuses (bias, activation, Dropout, folded inference BatchNorm), then its
         BatchNorm + LeakyReLU pass where it has one of its own."""
         if st.ln is not None: return self.ln_forward(ctx, i, st, xin, out)      # noqa: E701
+        if st.pn is not None: return self.pn_forward(ctx, i, st, xin, out)      # noqa: E701
         bias = st.lin.vars.get("bias")
         tgt = ctx.z[i] if st.bn is not None else out
         stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
@@ -662,6 +681,7 @@ class Net:
         image gradient of x-hat.  ``defer_conv_dw``: the conv filter gradients are left to ``gp_second_order_merged`` (bias
         and Dense gradients are still taken here).  ``keep_u_rows`` = (lo, hi): LayerNormalization stages keep u, the gradient at
         their normalised pre-activation, for those samples (the x-hat rows: gp_second_order's source term needs it)."""
+        if need_dx and self.latent_pn is not None: raise NotImplementedError("the gradient at the input of a network that starts with a PixelNormalization (the latents' normalisation has no backward)")  # noqa: E701
         if need_dw:
             self.store.ensure_opt_state()
         p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active(),
@@ -705,6 +725,7 @@ class Net:
         if st.bn is not None:
             return self._bn_backward(p, i, st, gv)
         if st.ln is not None: return self.ln_backward(p, i, st, gv)      # noqa: E701
+        if st.pn is not None: return self.pn_backward(p, i, st, gv)      # noqa: E701
         if st.act == "tanh":
             return ops.tanh_bwd(gv, ctx.a[i], ctx.buf(ctx.dz, i))
         if st.act != "lrelu" or g_is_dz:
@@ -797,9 +818,10 @@ class Net:
         ctx = p.ctx
         if st.kind == "mbstd": return self.mbstd_backward(p, i, st, prev, dz)      # noqa: E701
         fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
-        # the gradient at an LN stage's output lands in that stage's dz buffer and is turned into dz in place -- except where a row
-        # exceeds what a wave holds in registers (ops.layernorm.route: chunks > 1), where the kernel wants a buffer of its own
-        below = ctx.gin if prev is not None and prev.ln is not None and ops.layernorm.route(prev.out_shape[-1])["chunks"] > 1 else ctx.dz
+        # the gradient at an LN (or PixelNormalization) stage's output lands in that stage's dz buffer and is turned into dz in place
+        # -- except where a row exceeds what a wave holds in registers (ops.layernorm.route / ops.pixelnorm.route: chunks > 1), where
+        # the kernel wants a buffer of its own
+        below = ctx.gin if prev is not None and self.rereads_rows(prev) else ctx.dz
         tgt = (ctx.buf(below, i - 1) if i > 0 else ctx.input_grad()).view(ctx.B, *st.in_shape)
         if st.kind == "upsample":           # transpose of the upsample
             ops.pool2x_sum(dz.view(ctx.B, *st.out_shape), tgt, 1.0)
@@ -821,6 +843,56 @@ class Net:
             else:
                 self._conv(st, dz, tgt, True, EPI_NONE)
         return tgt, fuse
+
+    @staticmethod
+    def rereads_rows(st):
+        """Whether the backward of ``st``'s normalisation reads a row from memory twice (the chunked route of its kernels), so that
+        its output must not overwrite the incoming gradient."""
+        if st.ln is not None:
+            return ops.layernorm.route(st.out_shape[-1])["chunks"] > 1
+        return st.pn is not None and ops.pixelnorm.route(st.pn_channels)["chunks"] > 1
+
+    # ---- PixelNormalization (DESIGN.md §5 "Pixel normalisation").  Public names for the reason the LayerNormalization helpers
+    # carry them: no configuration of the engine-trace fixture has the layer; tests/test_pixelnorm_cpu.py records what these enqueue.
+    PN_RULE = ("PixelNormalization is supported directly behind the LeakyReLU of a Dense (through its Reshape), Conv2D or Conv2DTranspose "
+               "stage without BatchNormalization, LayerNormalization, Dropout or tanh, or as the network's first layer on a [C] vector")
+
+    def pn_place(self, flat_layers, idx, cur):
+        """Net.__init__'s placement rule for the PixelNormalization at ``flat_layers[idx]``: the latents' normalisation, or the
+        normalisation of stage ``cur``; everything else is refused."""
+        l, s = flat_layers[idx]
+        if idx == 0:
+            if len(s) != 1:
+                raise NotImplementedError(self.PN_RULE + f" (first layer on an input of shape {tuple(s)})")
+            self.latent_pn = l
+            return
+        ok = (cur is not None and cur.kind in ("dense", "conv", "convT") and cur.act == "lrelu" and flat_layers[idx - 1][0].kind == "lrelu"
+              and cur.bn is None and cur.ln is None and not cur.drop and cur.pn is None)
+        if not ok:
+            raise NotImplementedError(self.PN_RULE)
+        cur.pn, cur.pn_channels = l, int(s[-1])
+
+    def pn_latents(self, ctx, x):
+        """The latents' normalisation: one launch into a buffer of the pass's own, nothing kept (it has no backward)."""
+        if "pn_latents" not in ctx._extra:
+            ctx._extra["pn_latents"] = torch.empty((ctx.B,) + self.in_shape, dtype=torch.float32, device=self.device)
+        return ops.pixelnorm.fwd(x.view(ctx.B, *self.in_shape), ctx._extra["pn_latents"], ctx.B, self.in_shape[0], eps=self.latent_pn.epsilon)
+
+    def pn_forward(self, ctx, i, st, xin, out):
+        """The linear op (+ bias) into ctx.z[i], then out = PixelNorm(LeakyReLU(z)) of stage i in one pass; the rows' r stays in
+        ctx.inv[i].  The same in training and in inference."""
+        z, bias = ctx.z[i], st.lin.vars.get("bias")
+        if st.kind == "dense":
+            ops.gemm(xin, self.store.kernel(st.lin), z, ctx.B, st.out_shape[0], st.in_shape[0], bias=bias)
+        else:
+            self._conv(st, xin, z, False, EPI_NONE, bias=bias)
+        ops.pixelnorm.fwd(z, out, ctx.B * st.pn_rows, st.pn_channels, r=ctx.inv[i], eps=st.pn.epsilon, lrelu_alpha=st.alpha)
+
+    def pn_backward(self, p, i, st, gv):
+        """Through stage i's PixelNormalization and LeakyReLU in one pass, from the stage's stored output: dz, in place where the
+        gradient already stands in the stage's dz buffer (_input_grad put it there)."""
+        ctx = p.ctx
+        return ops.pixelnorm.bwd(gv, ctx.a[i], ctx.inv[i], ctx.buf(ctx.dz, i), ctx.B * st.pn_rows, st.pn_channels, lrelu_alpha=st.alpha)
 
     # ---- DiffAugment in front of stage 0 (DESIGN.md §5 "Augmentation").  Public names for the reason the LayerNormalization helpers
     # carry them: the engine-trace fixture's configurations run without augmentation; tests/test_diffaug_cpu.py records these.
@@ -893,6 +965,7 @@ class Net:
 
         Not with LayerNormalization stages: their source backward (gp_ln_source_backward) needs the x-hat rows of the activations
         this pass overwrites, so such a critic takes ``gp_second_order`` on ``ctx.rows(lo, hi)``."""
+        if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()
         if set(kinds) & set(SOURCE_KINDS): raise NotImplementedError("gp_second_order_merged overwrites activations the LayerNormalization / MinibatchStdDev source backward needs")  # noqa: E701
         self.store.ensure_opt_state()
@@ -911,6 +984,7 @@ class Net:
         A LayerNormalization stage is not piecewise linear: its tangent is gp_ln_stage's, and what the linearised forward's
         dependence on the stage's PRIMAL input adds goes down the network once more in gp_ln_source_backward.  That pass writes the
         last contribution to every layer up to the top-most such stage, so those layers' slices go to the reducer from there."""
+        if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()
         self.store.ensure_opt_state()
         top = max((i for i, k in enumerate(kinds) if k in SOURCE_KINDS), default=-1)
@@ -1024,7 +1098,7 @@ class Net:
         """_input_grad of a MinibatchStdDev stage: the gradient at its input into the buffer the stage below reads its output
         gradient from (that stage's LeakyReLU' / Dropout' follow in its own launch); the groups' q stays for the penalty's source."""
         ctx = p.ctx
-        below = ctx.gin if prev.ln is not None and ops.layernorm.route(prev.out_shape[-1])["chunks"] > 1 else ctx.dz
+        below = ctx.gin if self.rereads_rows(prev) else ctx.dz
         tgt = ctx.buf(below, i - 1).view(ctx.B, *st.in_shape)
         mu, rs, _, q = ctx.mbstd_stats(i)[:4]
         ops.mbstd.bwd(dz.view(ctx.B, *st.out_shape), ctx.xin[i], mu, rs, tgt, q, st.lin.group_size)

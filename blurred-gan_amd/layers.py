@@ -171,6 +171,26 @@ class LayerNormalization(Layer):
         return [("gamma", (c,), True, _ones((c,))), ("beta", (c,), True, _zeros((c,)))]
 
 
+class PixelNormalization(Layer):
+    """The pixel-wise feature normalisation of ProGAN / StyleGAN generators (Karras et al. 2018): every pixel's C channels -- the last
+    axis of an [H, W, C] map, or a [C] latent vector -- are divided by their root mean square, y = a / sqrt(mean_c(a^2) + epsilon).
+    No variables and no state; the same in training and in inference, and nothing couples the samples of a batch.  It stands
+    directly behind the LeakyReLU of a generator stage (in place of BatchNormalization in front of it), or first in the network,
+    where it normalises the latents."""
+    kind = "pixelnorm"
+
+    def __init__(self, epsilon=1e-8, **kw):
+        super().__init__(**kw)
+        if not float(epsilon) > 0.0:
+            raise ValueError(f"PixelNormalization epsilon={epsilon!r}: must be positive")
+        self.epsilon = float(epsilon)
+
+    def out_shape(self, s):
+        if len(s) not in (1, 3):
+            raise NotImplementedError(f"PixelNormalization needs an [H, W, C] map or a [C] vector, got {tuple(s)}")
+        return tuple(s)
+
+
 def _normalize(x):
     """x / max(||x||, 1e-12): the normalisation of the power iteration."""
     return x / max(float(np.linalg.norm(x)), 1e-12)

@@ -19,6 +19,14 @@ block gains 2 * C variables; it combines with ``downsampling="pool"``.
 Dense kernel becomes [P * (C + 1), 1] (flattened in (H, W, C + 1) order); the batch size must be a multiple of G.  It combines with
 ``downsampling="pool"``, ``normalization="layer"`` and ``spectral_norm=True``.
 
+The generator takes ``normalization="pixel"`` (default ``"batch"``: the reference's stack): no BatchNormalization anywhere; the Dense
+and every hidden (transposed) convolution carry a bias, and each hidden block is LeakyReLU -> ``layers.PixelNormalization`` (the
+ProGAN / StyleGAN generator's normalisation: per pixel, no variables, no statistics, the same in training and inference, nothing
+shared across the batch or across data-parallel ranks).  The Dense's block is Dense -> Reshape -> LeakyReLU -> PixelNormalization: the
+normalisation runs over the channels of the reshaped map.  The tanh output layer is unchanged.  ``normalize_latents=True`` puts a
+PixelNormalization in front of the Dense (with either normalisation).  Both combine with ``upsampling="resize"`` and
+``spectral_norm=True``.
+
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
 engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``."""
 from __future__ import annotations
@@ -42,30 +50,47 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 
 class DCGANGenerator(layers.SpectralSequential):
-    def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, **kwargs):
+    def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, normalization="batch",
+                 normalize_latents=False, **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm = bool(spectral_norm)
         if upsampling not in ("transpose", "resize"):
             raise ValueError(f"upsampling must be 'transpose' or 'resize', got {upsampling!r}")
-        self.upsampling = upsampling
+        if normalization not in ("batch", "pixel"):
+            raise ValueError(f"normalization must be 'batch' or 'pixel', got {normalization!r}")
+        self.upsampling, self.normalization, self.normalize_latents = upsampling, normalization, bool(normalize_latents)
+        pixel = normalization == "pixel"
         base, ch, convt, last = _G[arch]
         k = KSIZE.get(arch, 5)
         self.latent_size = latent_size or LATENT[arch]
-        self.add(layers.Dense(base * base * ch, use_bias=False, input_shape=(self.latent_size,)))
-        self.add(layers.BatchNormalization())
-        self.add(layers.LeakyReLU())
-        self.add(layers.Reshape((base, base, ch)))
+        first = dict(input_shape=(self.latent_size,))
+        if self.normalize_latents:
+            self.add(layers.PixelNormalization(**first))
+            first = {}
+        self.add(layers.Dense(base * base * ch, use_bias=pixel, **first))
+        if pixel:
+            self.add(layers.Reshape((base, base, ch)))
+            self.add(layers.LeakyReLU())
+            self.add(layers.PixelNormalization())
+        else:
+            self.add(layers.BatchNormalization())
+            self.add(layers.LeakyReLU())
+            self.add(layers.Reshape((base, base, ch)))
         assert self.output_shape == (None, base, base, ch)
         hw = base
         for filters, stride, act in convt:
             if stride == 2 and upsampling == "resize":
                 self.add(layers.UpSampling2D())
-                self.add(layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=False, activation=act))
+                self.add(layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=pixel and act is None, activation=act))
             else:
-                self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=False, activation=act))
+                self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=pixel and act is None,
+                                                activation=act))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
-            if act is None:
+            if act is None and pixel:
+                self.add(layers.LeakyReLU())
+                self.add(layers.PixelNormalization())
+            elif act is None:
                 self.add(layers.BatchNormalization())
                 self.add(layers.LeakyReLU())
         if last is not None:

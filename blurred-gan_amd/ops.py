@@ -417,6 +417,38 @@ class layernorm:
         return s
 
 
+# ------------------------------------------------------------------ pixel normalisation (include/bgan.h "pixel normalisation")
+class pixelnorm:
+    """The PixelNormalization kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's
+    public functions by name; these calls are recorded by the pixel normalisation tests' own recorder."""
+
+    @staticmethod
+    def route(Cc, aligned=True):
+        """How the kernels lay a row of ``Cc`` channels over a wave: dict(vec, lanes, regs, chunks, rows_per_workgroup) of a call
+        whose matrices are all 16-byte aligned (``aligned=False``: of one with a misaligned view)."""
+        v = (C.c_int * _lib.PIXELNORM_ROUTE_INTS)()
+        check(_lib.load().bg_pixelnorm_route(int(Cc), v), "bg_pixelnorm_route")
+        vec, lanes, regs, chunks = v[0:4] if aligned else v[4:8]
+        return dict(vec=vec, lanes=lanes, regs=regs, chunks=chunks, rows_per_workgroup=4 * (64 // lanes))
+
+    @staticmethod
+    def fwd(x, y, R, Cc, r=None, eps=1e-8, lrelu_alpha=1.0):
+        """y = a / sqrt(mean(a^2) + eps) over the rows of a = LeakyReLU(x) [R, Cc]; ``r`` keeps the rows' 1 / sqrt(...) for bwd."""
+        _f32(x, y, r)
+        assert x.numel() == R * Cc == y.numel() and (r is None or r.numel() >= R)
+        check(_lib.load().bg_pixelnorm_fwd_f32(_ptr(x), _ptr(y), _ptr(r), R, Cc, eps, lrelu_alpha, _stream()), "bg_pixelnorm_fwd_f32")
+        return y
+
+    @staticmethod
+    def bwd(g, y, r, dz, R, Cc, lrelu_alpha=1.0):
+        """dz = LeakyReLU' * r * (g - y * mean(g * y)): through the normalisation and the LeakyReLU in front of it; may run in place
+        (dz is g) where the route has one chunk."""
+        _f32(g, y, r, dz)
+        assert g.numel() == R * Cc == y.numel() == dz.numel() and r.numel() >= R
+        check(_lib.load().bg_pixelnorm_bwd_f32(_ptr(g), _ptr(y), _ptr(r), _ptr(dz), R, Cc, lrelu_alpha, _stream()), "bg_pixelnorm_bwd_f32")
+        return dz
+
+
 # ------------------------------------------------------------------ differentiable augmentation (include/bgan.h)
 class diffaug:
     """The DiffAugment kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's public

@@ -133,6 +133,10 @@ class WGAN:
         self.generator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.discriminator = discriminator
         self.discriminator.build()
+        if any(l.kind == "pixelnorm" for l, _ in self.discriminator.flat_layers()):
+            raise NotImplementedError("PixelNormalization in the discriminator: the layer is the generator's normalisation; a critic with "
+                                      "it has no gradient-penalty route (PixelNormalization in a critic under the gradient penalty is not "
+                                      "built)")
         self.discriminator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.d_steps_per_g_step = self.hparams.d_steps_per_g_step
         self.batch_size = None

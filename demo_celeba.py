@@ -29,27 +29,41 @@ def make_dataset(batch_size, n_batches=None, seed=0):
 class DCGANGenerator(layers.SpectralSequential):
     """demo_celeba.py:51-93."""
 
-    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, normalization="batch", normalize_latents=False,
+                 **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm = bool(spectral_norm)
         self.latent_size = latent_size
         resize = {"transpose": False, "resize": True}[upsampling]
-        self.add(layers.Dense(4 * 4 * 512, use_bias=False, input_shape=(self.latent_size,)))
-        self.add(layers.BatchNormalization())
-        self.add(layers.LeakyReLU())
-        self.add(layers.Reshape((4, 4, 512)))
+        pixel = {"batch": False, "pixel": True}[normalization]
+
+        def block(reshape=None):      # behind a linear layer: the reference's BatchNormalization -> LeakyReLU, or LeakyReLU -> PixelNormalization
+            if pixel and reshape:
+                self.add(layers.Reshape(reshape))
+            if not pixel:
+                self.add(layers.BatchNormalization())
+            self.add(layers.LeakyReLU())
+            if pixel:
+                self.add(layers.PixelNormalization())
+            elif reshape:
+                self.add(layers.Reshape(reshape))
+        first = dict(input_shape=(self.latent_size,))
+        if normalize_latents:
+            self.add(layers.PixelNormalization(**first))
+            first = {}
+        self.add(layers.Dense(4 * 4 * 512, use_bias=pixel, **first))
+        block(reshape=(4, 4, 512))
         assert self.output_shape == (None, 4, 4, 512)
         hw = 4
         for filters, stride in ((512, 1), (256, 2), (128, 2), (64, 2), (32, 2), (16, 2)):
             if resize and stride == 2:      # resize-convolution: nearest-neighbour upsampling, then a stride-1 convolution
                 self.add(layers.UpSampling2D())
-                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=False))
+                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=pixel))
             else:
-                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding='same', use_bias=False))
+                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding='same', use_bias=pixel))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
-            self.add(layers.BatchNormalization())
-            self.add(layers.LeakyReLU())
+            block()
         self.add(layers.Conv2D(3, (5, 5), padding='same', use_bias=False, activation='tanh'))
         assert self.output_shape == (None, 128, 128, 3), self.output_shape
 
@@ -102,6 +116,12 @@ def make_parser():
     parser.add_argument("--critic-mbstd", dest="critic_mbstd", type=int, default=0, metavar="G",
                         help="minibatch standard deviation layer in front of the critic's head, over groups of G consecutive samples "
                              "(0: off; the batch size must be a multiple of G)")
+    parser.add_argument("--generator-norm", dest="generator_norm", default="batch", choices=["batch", "pixel"],
+                        help="generator normalisation: BatchNormalization in front of every LeakyReLU (default, the reference's) or a "
+                             "PixelNormalization behind it (ProGAN / StyleGAN: per pixel, no variables, no batch statistics; the Dense "
+                             "and the hidden convolutions then carry a bias)")
+    parser.add_argument("--normalize-latents", dest="normalize_latents", action="store_true",
+                        help="a PixelNormalization of the latent vectors in front of the generator's Dense")
     parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
                         help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
                              "the generator average)")
@@ -157,7 +177,8 @@ def main(argv=None):
         total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
-    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm)
+    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
+                         normalize_latents=args.normalize_latents)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
                               minibatch_stddev=args.critic_mbstd)
     generator_ema = None

@@ -31,31 +31,44 @@ def make_dataset(batch_size, n_batches=None, shuffle_buffer_size=256, seed=0):
 class DCGANGenerator(layers.SpectralSequential):
     """demo_mnist.py:48-71."""
 
-    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, **kwargs):
+    def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, normalization="batch", normalize_latents=False,
+                 **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm = bool(spectral_norm)
         self.latent_size = latent_size
         resize = {"transpose": False, "resize": True}[upsampling]
+        pixel = {"batch": False, "pixel": True}[normalization]
+
+        def block(reshape=None):      # behind a linear layer: the reference's BatchNormalization -> LeakyReLU, or LeakyReLU -> PixelNormalization
+            if pixel and reshape:
+                self.add(layers.Reshape(reshape))
+            if not pixel:
+                self.add(layers.BatchNormalization())
+            self.add(layers.LeakyReLU())
+            if pixel:
+                self.add(layers.PixelNormalization())
+            elif reshape:
+                self.add(layers.Reshape(reshape))
+        first = dict(input_shape=(self.latent_size,))
+        if normalize_latents:
+            self.add(layers.PixelNormalization(**first))
+            first = {}
 
         def up2(filters, **kw):       # a resolution step: the reference's stride-2 Conv2DTranspose, or upsampling + stride-1 Conv2D
             if resize:
                 self.add(layers.UpSampling2D())
-                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=False, **kw))
+                self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=pixel and not kw, **kw))
             else:
-                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(2, 2), padding='same', use_bias=False, **kw))
-        self.add(layers.Dense(7 * 7 * 256, use_bias=False, input_shape=(self.latent_size,)))
-        self.add(layers.BatchNormalization())
-        self.add(layers.LeakyReLU())
-        self.add(layers.Reshape((7, 7, 256)))
+                self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(2, 2), padding='same', use_bias=pixel and not kw, **kw))
+        self.add(layers.Dense(7 * 7 * 256, use_bias=pixel, **first))
+        block(reshape=(7, 7, 256))
         assert self.output_shape == (None, 7, 7, 256)
-        self.add(layers.Conv2DTranspose(128, (5, 5), strides=(1, 1), padding='same', use_bias=False))
+        self.add(layers.Conv2DTranspose(128, (5, 5), strides=(1, 1), padding='same', use_bias=pixel))
         assert self.output_shape == (None, 7, 7, 128)
-        self.add(layers.BatchNormalization())
-        self.add(layers.LeakyReLU())
+        block()
         up2(64)
         assert self.output_shape == (None, 14, 14, 64)
-        self.add(layers.BatchNormalization())
-        self.add(layers.LeakyReLU())
+        block()
         up2(1, activation='tanh')
         assert self.output_shape == (None, 28, 28, 1)
 
@@ -114,6 +127,12 @@ def make_parser():
     parser.add_argument("--critic-mbstd", dest="critic_mbstd", type=int, default=0, metavar="G",
                         help="minibatch standard deviation layer in front of the critic's head, over groups of G consecutive samples "
                              "(0: off; the batch size must be a multiple of G)")
+    parser.add_argument("--generator-norm", dest="generator_norm", default="batch", choices=["batch", "pixel"],
+                        help="generator normalisation: BatchNormalization in front of every LeakyReLU (default, the reference's) or a "
+                             "PixelNormalization behind it (ProGAN / StyleGAN: per pixel, no variables, no batch statistics; the Dense "
+                             "and the hidden convolutions then carry a bias)")
+    parser.add_argument("--normalize-latents", dest="normalize_latents", action="store_true",
+                        help="a PixelNormalization of the latent vectors in front of the generator's Dense")
     parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
                         help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
                              "the generator average)")
@@ -176,7 +195,8 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "mnist") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
-    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm)
+    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
+                         normalize_latents=args.normalize_latents)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
                               minibatch_stddev=args.critic_mbstd)
     generator_ema = None

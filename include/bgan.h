@@ -289,6 +289,27 @@ int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int
 int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float* s, int R, int C, const float* gamma, const float* mu,
                         const float* r, float* dgamma, float acc_beta, float acc_scale, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- pixel normalisation (Karras et al. 2018; layers.PixelNormalization) + the LeakyReLU in front of it, fp32 -----------------
+ * Data is [R, C]: R rows (the pixels of NHWC maps, or latent vectors) of C contiguous channels.  Per row, means over its C channels:
+ *   a = x > 0 ? x : lrelu_alpha * x   (lrelu_alpha = 1: the identity),   r = 1 / sqrt(mean(a^2) + eps),   y = a * r.
+ * The Jacobian of a -> y is r * (I - y y^T / C), and r > 0 gives sign(y) = sign(x), so the backward runs through the normalisation
+ * and the LeakyReLU in one pass from the stored output, r and the incoming gradient g alone (x is never re-read):
+ *   dz = (y > 0 ? 1 : lrelu_alpha) * r * (g - y * mean(g * y))          (the comparison is bg_mul_grad_f32's).
+ * No parameters, no workspace, no atomics: a row's sum is taken in a fixed order, the same bits on every run.
+ * Any R, C >= 1.  Pointers 4-byte aligned (BG_ERR_BAD_ALIGNMENT).  A call moves float4s where C % 4 == 0 and x, y, g, dz are all
+ * 16-byte aligned, single floats otherwise; no call is refused for a misaligned view.  bg_pixelnorm_route (host only):
+ * out[BG_PIXELNORM_ROUTE_INTS] = {floats per unit (4 or 1), lanes that share a row (64 / lanes rows per wave, four waves per
+ * workgroup), units a lane keeps in registers, chunks a row is swept in when it exceeds what one wave holds (1: read once)} of a
+ * call whose matrices are all 16-byte aligned, then the same four of a call with a misaligned one.  A refused call launches
+ * nothing.  No call takes a step-program binding. */
+#define BG_PIXELNORM_ROUTE_INTS 8
+int bg_pixelnorm_route(int C, int* out);
+/* y = a * r; r ([R] floats, kept for the backward) may be NULL: nothing is kept (latents, passes without a backward).  y may alias
+ * x where the call's route has chunks == 1 (BG_ERR_UNSUPPORTED otherwise). */
+int bg_pixelnorm_fwd_f32(const float* x, float* y, float* r /* may be NULL */, int R, int C, float eps, float lrelu_alpha, void* stream);
+/* dz as above.  dz may alias g where the call's route has chunks == 1; it must not alias y (BG_ERR_UNSUPPORTED). */
+int bg_pixelnorm_bwd_f32(const float* g, const float* y, const float* r, float* dz, int R, int C, float lrelu_alpha, void* stream);
+
 /* ---- differentiable augmentation (DiffAugment, Zhao et al. 2020) of the critic's input, NHWC fp32 -----------------------------
  * Per sample an affine map T(x) = L x + k of its [H, W, C] map: colour, then translation, then cutout.  ops_mask: bit 0 colour,
  * bit 1 translation, bit 2 cutout; an absent operation takes its neutral value and does no arithmetic (without colour values are
