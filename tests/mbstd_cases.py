@@ -29,7 +29,15 @@ CASES = [
     ("cut_one", 2200, 1, 1, 7),
     ("cut_two", 4, 2, 4, 1024),
     ("cut_ragged", 3, 2, 7, 911),
+    # more groups than the MAX_BLOCKS workgroups of a grid: three workgroups take a second group and reuse their LDS image (resident
+    # route); through the G = 2 branch with scalar columns (groups of 24 bytes: every other one's image sits 8 bytes into its LDS
+    # slot), and through the general one with float4 columns
+    ("second_trip", 2, 1027, 1, 3),
+    ("second_trip_g3", 3, 1026, 1, 8),
+    # GE = 524320 floats: ceil(GE / CUT_FLOATS) = 65, so the cap of MAX_CUTS holds for the columns; Ly = 524328 does the same for the emit
+    ("cut_capped", 2, 1, 4, 65540),
 ]
+MAX_BLOCKS, CUT_FLOATS, MAX_CUTS = 1024, 8192, 64      # csrc/mbstd.hip: kMaxBlocks, kCutFloats, kMaxCuts
 
 
 def case(name):

@@ -114,7 +114,7 @@ def test_plan_geometry(plans):
     for (name, call, off), p in plans.items():
         _, G, groups, P, Cc = MC.case(name)
         assert p["resident"] == (G * P * Cc <= MC.RESIDENT_FLOATS), (name, call)
-        assert p["threads"] == 256 and p["grid_x"] == groups
+        assert p["threads"] == 256 and p["grid_x"] == min(groups, MC.MAX_BLOCKS)
         assert p["launches"] == (1 if p["resident"] or call == "bwd" else 2)
         assert p["lds_bytes"] <= 64 * 1024
         if p["resident"]:
@@ -125,6 +125,32 @@ def test_plan_geometry(plans):
     assert ops.mbstd.workspace_bytes(8, 4, 4, 512) == 0
     assert ops.mbstd.workspace_bytes(8, 4, 4, 1024) == 4 * 2 * plans[("cut_two", "fwd", 0)]["grid_y"]
     assert plans[("celeba_top", "fwd", 0)]["resident"] and plans[("mnist_top", "fwd", 0)]["resident"]
+
+
+def test_case_list_reaches_a_second_group_per_workgroup_and_the_cap_on_cuts(plans):
+    """More groups than workgroups on the resident route (the LDS image is reused), through the G = 2 branch and the general one;
+    a group that would be cut more than MAX_CUTS ways, for the columns and for the emit."""
+    text = open(os.path.join(ROOT, "blurred-gan_amd", "csrc", "mbstd.hip")).read()
+    assert f"kMaxBlocks = {MC.MAX_BLOCKS};" in text and f"constexpr int kCutFloats = {MC.CUT_FLOATS};" in text
+    assert f"constexpr int kMaxCuts = {MC.MAX_CUTS};" in text and "p.gx = (unsigned)std::min(N / G, kMaxBlocks);" in text
+    for call in ("fwd", "bwd", "gp"):
+        second = [(name, G) for name, G, groups, P, Cc in MC.CASES for p in [plans[(name, call, 0)]]
+                  if p["resident"] and p["grid_x"] == MC.MAX_BLOCKS < groups and plans[(name, call, 1)]["grid_x"] == MC.MAX_BLOCKS]
+        assert [n for n, G in second if G == 2] and [n for n, G in second if G > 2], (call, second)
+        capped = []
+        for name, G, groups, P, Cc in MC.CASES:
+            p = plans[(name, call, 0)]
+            cols, emit = (G * P * Cc, G * P * (Cc + 1))
+            if not p["resident"] and p["grid_y"] == MC.MAX_CUTS == p["grid_y_emit"] and min(-(-cols // MC.CUT_FLOATS), -(-emit // MC.CUT_FLOATS)) > MC.MAX_CUTS:
+                capped.append(name)
+                assert p["trips_max"] >= 2 and p["vecs"] % MC.MAX_CUTS, name          # several trips per lane, a ragged last cut
+                if call != "bwd":
+                    assert ops.mbstd.workspace_bytes(G * groups, G, P, Cc) == 4 * groups * MC.MAX_CUTS
+        assert capped, call
+    # three workgroups take a second group; the capped group is one cut past the cap
+    assert MC.case("second_trip")[2] - MC.MAX_BLOCKS == 3 and MC.case("second_trip_g3")[2] - MC.MAX_BLOCKS == 2
+    _, G, _, P, Cc = MC.case("cut_capped")
+    assert -(-G * P * Cc // MC.CUT_FLOATS) == MC.MAX_CUTS + 1 == -(-G * P * (Cc + 1) // MC.CUT_FLOATS)
 
 
 # ------------------------------------------------------------------ 3. the layer

@@ -4,7 +4,8 @@ tests/mbstd_cases.py, once with all views 16-byte aligned and once with all of t
 Tolerance (the rule of tests/helpers.py): per element POINT_RTOL * |reference| + POINT_ATOL * max|reference|; where a float32 numpy
 evaluation of the same formulas does not meet that itself, YARDSTICK x its own largest deviation instead.  Every output and the
 kept statistics live in guarded buffers: nothing is written outside, every element inside is written, inputs stay as they were.
-Each run is repeated into fresh buffers: the same bits."""
+Each run is repeated into fresh buffers: the same bits.  A second group per workgroup on the two-launch route is held by bit identity
+with a small run of the same groups (the last test)."""
 import numpy as np
 import pytest
 import torch
@@ -30,16 +31,37 @@ def _close(got, ref, ref32, what):
     assert (err <= tol).all(), f"{what}: max|err| {err.max():.3e} at {np.unravel_index(err.argmax(), err.shape)} ({rule})"
 
 
+def tile_groups(flat, per_group, groups):
+    """[groups, per_group] on the device: the groups of ``flat`` (whole groups of per_group floats), repeated in order."""
+    small = flat.view(-1, per_group)
+    return small.repeat(-(-groups // small.shape[0]), 1)[:groups]
+
+
 class _Run:
     """One run of the three calls on guarded buffers at ``off`` floats past a 16-byte boundary."""
 
     def __init__(self, x, u, d, G, off, eps=EPS):
         N, P, C = x.shape
-        n = N // G
         g = lambda size, init=None: Guarded(size, init=init, offset=off)
         self.inputs = dict(x=g(x.size, x), u=g(u.size, u), d=g(d.size, d))
-        self.out = dict(y=g(N * P * (C + 1)), mu=g(n * P * C), rs=g(n * P * C), f=g(n), dx=g(x.size), q=g(n), vout=g(N * P * (C + 1)),
-                        src=g(x.size), fdot=g(n))
+        self._launch(N, P, C, G, off, eps)
+
+    @classmethod
+    def tiled(cls, small, groups, P, C, G, eps=EPS):
+        """``groups`` groups that repeat the groups of the run ``small`` in order (its inputs tiled on the device), 16-byte aligned."""
+        self = cls.__new__(cls)
+        self.inputs = {}
+        for key, per_group in (("x", G * P * C), ("u", G * P * (C + 1)), ("d", G * P * C)):
+            self.inputs[key] = Guarded(groups * per_group)
+            self.inputs[key].view.view(groups, per_group).copy_(tile_groups(small.inputs[key].view, per_group, groups))
+        self._launch(G * groups, P, C, G, 0, eps)
+        return self
+
+    def _launch(self, N, P, C, G, off, eps):
+        n = N // G
+        g = lambda size, init=None: Guarded(size, init=init, offset=off)
+        self.out = dict(y=g(N * P * (C + 1)), mu=g(n * P * C), rs=g(n * P * C), f=g(n), dx=g(N * P * C), q=g(n), vout=g(N * P * (C + 1)),
+                        src=g(N * P * C), fdot=g(n))
         nb = ops.mbstd.workspace_bytes(N, G, P, C)
         self.ws = g(nb // 4) if nb else None
         I, O = self.inputs, self.out
@@ -152,3 +174,36 @@ def test_zero_variance_columns_and_a_zero_variance_group(G, off):
     ref, ref32 = _references(x, u, d3.reshape(d.shape), G)
     got = _Run(x, u, d3.reshape(d.shape), G, off)
     _close(got.get("src"), ref["src"], ref32["src"], f"G={G} off={off} src with an unequal tangent on a constant column")
+
+
+def test_a_second_group_per_workgroup_on_the_two_launch_route_repeats_the_first():
+    """1027 groups of 15360 floats (the resident_first_out geometry: two launches, two cuts) for 1024 workgroup columns: three of them
+    take a second group.  The float64 formulas at that size would cost too much on the host, so: six groups are run on their own and
+    checked against the formulas as usual; the large run repeats those six in order, and every output of its group g must equal the
+    small run's group g % 6 bit for bit.  That rests on the kernels' contract: a group's bits depend on its data, its alignment (all
+    group bases 16-byte aligned here: 15360 floats apart) and its cut count, which depends on the group's size alone -- not on which
+    workgroup or which trip handles it.  Where the small run passes and this fails, the fault is in the second trip."""
+    _, G, _, P, C = MC.case("resident_first_out")
+    few, many = 6, MC.MAX_BLOCKS + 3
+    x, u, d = MC.data(G, few, P, C, seed=23)
+    ref, ref32 = _references(x, u, d, G)
+    small = _Run(x, u, d, G, 0)
+    small.check_buffers()
+    for key in small.out:
+        _close(small.get(key), ref[key], ref32[key], f"{few} groups {key}")
+    plan = {n: ops.mbstd.plan(G * n, G, P, C, "fwd") for n in (few, many)}
+    assert not plan[many]["resident"] and plan[many]["grid_x"] == MC.MAX_BLOCKS < many and plan[many]["launches"] == 2
+    assert plan[many]["grid_y"] == plan[few]["grid_y"] > 1 and plan[many]["grid_y_emit"] == plan[few]["grid_y_emit"]
+    big = _Run.tiled(small, many, P, C, G)
+    for name, b in {**big.inputs, **big.out, "ws": big.ws}.items():
+        assert b.guards_intact(), f"{name}: written outside"
+    per_group = dict(x=G * P * C, u=G * P * (C + 1), d=G * P * C, y=G * P * (C + 1), mu=P * C, rs=P * C, f=1, dx=G * P * C, q=1,
+                     vout=G * P * (C + 1), src=G * P * C, fdot=1)
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for key, b in big.inputs.items():
+        assert torch.equal(bits(b.view.view(many, -1)), bits(tile_groups(small.inputs[key].view, per_group[key], many))), f"{key}: input changed"
+    for key, b in big.out.items():
+        assert not bool(torch.isnan(b.view).any()), f"{key}: elements left unwritten"
+        got, want = bits(b.view.view(many, per_group[key])), bits(tile_groups(small.out[key].view, per_group[key], many))
+        wrong = (got != want).any(1)
+        assert not bool(wrong.any()), f"{key}: groups {torch.nonzero(wrong).flatten().tolist()[:8]} differ from the small run's"

@@ -31,6 +31,15 @@ LAZY_R1 = bg.Objective("nonsaturating", penalty_target=0.0, penalty_on="reals", 
 #   layernorm  (2.8e-05, 2.4, 2.5e-04) (1.2e-04, 2, 5.0e-04) (2.9e-07, 1.6, 1.9e-04) (3.2e-06, 1.6, 3.4e-04) (3.7e-06, 3.3, 4.9e-03)
 #   lazy       (1.2e-05, 0.041, 1.3e-04) (2.7e-05, 0.056, 1.8e-04) (1.7e-05, 0.058, 1.0e-04) (2.3e-06, 0.086, 1.0e-04) (4.6e-06, 0.06, 1.4e-04)
 #              (its step without the penalty: the same kinks, no x-hat pass)
+#   two_launch, the "mnist" critic at G = 4 (a group of 4 * 49 * 128 = 25088 floats, which needs the workspace):
+#              (2.1e-07, 0.09, 6.0e-04) (2.6e-07, 0.089, 3.0e-04) (4.8e-08, 0.09, 4.2e-04) (2.1e-07, 0.092, 2.7e-04) (2.5e-07, 0.1, 4.4e-04)
+#              No seed can pass KINK there: a step of the "mnist" pair has 552 000 LeakyReLU pre-activations (18 816 per sample
+#              in the critic's four passes, 31 360 in the generator's two), about 25 of them within 5e-6 of zero on average; none
+#              of the seeds 1-60 keeps its nearest further out than that.  The variant therefore takes the smallest critic on
+#              "tiny" images whose top leaves the resident route at G = 4 instead (wide_top_critic: 4 * 64 * 64 = 16384 floats
+#              per group, 65 536 pre-activations a step), where about one seed in nine passes:
+#   two_launch (2.3e-07, 0.24, 1.8e-03) (6.6e-07, 0.25, 9.4e-04) (2.5e-06, 0.24, 7.4e-04) (2.7e-06, 0.25, 2.2e-03) (1.0e-06, 0.27, 1.6e-03)
+#              the first seeds that pass: 17 (1.0e-05, 0.26, 1.4e-03), 31 (6.2e-06, 0.27, 6.6e-04), 40 (5.8e-06, 0.26, 9.0e-04)
 VARIANTS = {
     "plain": (1, {}, 2, {}),
     "g4": (2, {}, 4, {}),
@@ -38,12 +47,25 @@ VARIANTS = {
     "pool": (3, dict(downsampling="pool"), 2, {}),
     "layernorm": (1, dict(normalization="layer"), 2, {}),
     "lazy": (2, {}, 2, dict(objective=LAZY_R1, std=0.9)),
+    "two_launch": (17, None, 4, {}),
 }
+WIDE_TOP = (8, 8, 64)       # the map in front of two_launch's layer
+
+
+def wide_top_critic(G):
+    """One 5x5 convolution to 64 channels at full size, LeakyReLU, Dropout, the layer, the head: at batch 4 and G = 4 a group holds
+    4 * 8 * 8 * 64 = 16384 floats, more than the resident route takes, so forward and penalty call go through the workspace."""
+    from blurred_gan_amd import layers as L
+    m = L.SpectralSequential()
+    for layer in (L.Conv2D(WIDE_TOP[2], 5, strides=1, padding="same", input_shape=list(models.IMAGE_SHAPE["tiny"])), L.LeakyReLU(), L.Dropout(0.3),
+                  L.MinibatchStdDev(group_size=G), L.Flatten(), L.Dense(1, activation="linear")):
+        m.add(layer)
+    return m
 
 
 def case(name, device=None, seed=None, **kw):
     s, critic, G, mk = VARIANTS[name]
-    disc = lambda: models.DCGANDiscriminator(arch="tiny", minibatch_stddev=G, **critic)
+    disc = (lambda: wide_top_critic(G)) if critic is None else (lambda: models.DCGANDiscriminator(arch="tiny", minibatch_stddev=G, **critic))
     return OR.make_gan("tiny", 4, s if seed is None else seed, gbs=5, device=device, disc=disc, **mk, **kw)
 
 
@@ -137,6 +159,21 @@ def test_step_gradients_match_torch_with_layer_normalization():
     gan, _ = _step_case("layernorm")
     net = gan.discriminator.net()
     assert net.has_ln and net._gp_kinds() == ["ln", "ln", "mbstd", "dense"]
+
+
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_step_gradients_match_torch_on_the_two_launch_route(config):
+    """A top too large for the resident route: the engine sizes the workspace and shares it between the forward (all rows of the
+    pass) and the penalty call (the x-hat rows); both take two launches."""
+    from blurred_gan_amd import ops
+    B, G, (H, W, C) = 4, VARIANTS["two_launch"][2], WIDE_TOP
+    for rows in (B, 2 * B, 3 * B):
+        assert ops.mbstd.workspace_bytes(rows, G, H * W, C) > 0 and not ops.mbstd.plan(rows, G, H * W, C, "gp")["resident"]
+    gan, _ = _step_case("two_launch", CONFIGS[config])
+    net = gan.discriminator.net()
+    assert [st.kind for st in net.stages] == ["conv", "mbstd", "dense"] and gan.batch_size == B
+    st = net.stages[1]
+    assert (st.lin.group_size, st.ln_pixels, tuple(st.in_shape)) == (G, H * W, WIDE_TOP)
 
 
 @pytest.mark.parametrize("n_batches", [0, 1])
