@@ -1,6 +1,7 @@
 // Shared host-side plumbing for libbgan_hip.so: status/error strings, launch wrapper, profiling hooks.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -58,6 +59,12 @@ inline int fail(int code, const char* fmt, ...) {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// Workgroups of a 1-D grid-stride launch over n elements, per_thread of them to a thread per trip: enough to cover n, at most
+// 256 * 8 (eight workgroups of 256 threads for each of the chip's 256 compute units), never none.
+inline unsigned grid_cap(size_t n, int threads, int per_thread = 1) {
+  return (unsigned)std::max<size_t>(1, std::min<size_t>(cdiv(n, (size_t)threads * per_thread), 256 * 8));
+}
 
 // Scoped launch bracket: records profiling events, checks the launch.  While a step program is being recorded the bracket
 // leaves its name / flops / bytes in the program as well, so that a replay under bg_prof_enable(1) produces the same records.

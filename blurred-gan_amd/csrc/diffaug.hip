@@ -17,6 +17,7 @@
 // gridDim.y so that a small batch of large images still fills the chip (every workgroup of a sample repeats sweep 1 in the same
 // order: the same mean, bit for bit).
 #include "common.h"
+#include "reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -72,20 +73,8 @@ __host__ __device__ inline Draw decode(const float* u, const Geo& g) {
 
 inline int round_half_up(int extent, float ratio) { return (int)floorf((float)extent * ratio + 0.5f); }
 
-// f1(o) for the scalar head and tail, f4(o) for every float4 of the flat range [0, E) of a sample that starts at byte address
-// ``addr`` (4-byte aligned): o of an f4 call is 16-byte aligned in memory.  The float4s are dealt to the K workgroups of the sample
-// in contiguous runs (k-th of K); the head goes with the first run, the tail with the last.
-template <class F4, class F1>
-__device__ __forceinline__ void sweep(uintptr_t addr, int E, int k, int K, F4 f4, F1 f1) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  int head = (int)(((16u - (unsigned)(addr & 15u)) & 15u) >> 2);
-  head = head < E ? head : E;
-  const int nvec = (E - head) >> 2, tail0 = head + 4 * nvec;
-  const int per = (nvec + K - 1) / K, vlo = k * per, vhi = vlo + per < nvec ? vlo + per : nvec;
-  if (k == 0 && tid < head) f1(tid);
-  for (int v = vlo + tid; v < vhi; v += T) f4(head + 4 * v);
-  if (k == K - 1 && tid < E - tail0) f1(tail0 + tid);
-}
+using bg::block_sum;      // reduce.h: the workgroup's sum; red may still be read from the previous sample, hence its first barrier
+using bg::sweep;          // reduce.h: scalar head, float4 runs dealt to the K workgroups of the sample, scalar tail
 
 // sweep() over a whole sample for reading: the float4s are LOADED kBatch at a time per lane (ld) before any is consumed (use), so a
 // lane waits for memory once per batch (three: a 64 x 64 x 3 sample in one batch of a 1024-thread workgroup, in 64 registers); they are consumed in the loop's own order, which keeps a lane's partial sum's bits
@@ -106,17 +95,6 @@ __device__ __forceinline__ void sweep_read(uintptr_t addr, int E, Ld ld, Use use
       if (v + u * T < nvec) use(head + 4 * (v + u * T), r[u]);
   }
   if (tid < E - tail0) f1(tail0 + tid);
-}
-
-// sum over the workgroup in a fixed order; every thread gets it
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                                       // red may still be read from the previous sample
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = red[0];
-  for (int w = 1, nw = blockDim.x >> 6; w < nw; ++w) s += red[w];
-  return s;
 }
 
 // ADJ = false:  y = T(x) (linear: L x).   ADJ = true:  dx = L^T g.

@@ -12,7 +12,7 @@ namespace {
 constexpr int kT = 256;
 typedef float f32x4 __attribute__((ext_vector_type(4)));      // a native vector: its store stays ONE 16-byte instruction
 
-inline unsigned grid_for(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>(bg::cdiv(n, (size_t)kT), 256 * 8)); }
+inline unsigned grid_for(size_t n) { return bg::grid_cap(n, kT); }
 
 // [TF] resize_bilinear, half_pixel_centers: in = (out + 0.5) * scale - 0.5; lower = max(floor(in), 0),
 // upper = min(ceil(in), size - 1), lerp = in - floor(in)

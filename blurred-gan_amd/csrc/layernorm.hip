@@ -6,103 +6,21 @@
 // Per row, with all means over the row's C channels: mu, r = 1/sqrt(var + eps) (biased variance; saved by the forward),
 // xh = (z - mu) * r, and the Jacobian of z -> xh is the symmetric operator  M y = r * (yc - xh * mean(yc * xh)),  yc = y - mean(y).
 //
-// Routes (bg_ln_route reports the one a C takes).  A row is read in units of one float4 (C % 4 == 0) or one float (any other C):
-// U = C / 4 or C units.  L = the power of two >= U, at most 64, lanes share a row, so a wave holds 64 / L rows; with U > 64 each
-// lane keeps 2 or 4 units (U <= 128, U <= 256).  Up to there a row is read ONCE and stays in registers between its statistics and
-// its use.  Beyond (C > 1024, or C > 256 and not a multiple of 4) the row is cut into chunks of 64 units, one per lane, along
-// gridDim.y: a workgroup sweeps the whole row from memory for the statistics (the re-read hits L2) and keeps only its own chunk in
-// registers.  (One unit per lane there: with more, the sweeps' address and mask bookkeeping no longer fits the scalar registers.)
-// A workgroup is 4 waves = 4 * 64 / L rows per visit, in a grid-stride loop over at most 1024 workgroups.
+// Routes (bg_ln_route reports the one a C takes): csrc/rowwise.h's, float4 units for every C % 4 == 0 (the entry points refuse a
+// misaligned pointer there).  Up to 256 units a row is read ONCE and stays in registers between its statistics and its use, so an
+// output may alias the input it replaces; on the chunked route beyond, the row is swept again and it may not.
 //
 // Column sums (dgamma, dbeta) are deterministic: each lane adds its own channels over the rows it visits, in visit order; the
 // lanes of a wave that share a channel are folded by a fixed shuffle tree, the four waves through LDS in wave order, and one
 // partial row per workgroup goes to the workspace; ln_finish_kernel adds the partial rows in a fixed order (64 strided lanes and
 // a shuffle tree per channel).  No atomics: two runs give the same bits.  LDS holds that cross-wave scratch and nothing else.
 #include "common.h"
-#include <algorithm>
+#include "reduce.h"
+#include "rowwise.h"
 
 namespace {
 
-constexpr int kT = 256, kWaves = kT / 64, kMaxBlocks = 1024, kChunkUnits = 64;
-
-struct Route { int vec, lg, nv, chunks; };
-
-inline Route route_for(int C) {
-  Route t;
-  t.vec = C % 4 == 0 ? 4 : 1;
-  const int U = C / t.vec;
-  t.lg = 0;
-  while ((1 << t.lg) < U && t.lg < 6) ++t.lg;
-  const int per = (U + 63) / 64;
-  t.nv = per <= 1 ? 1 : per <= 2 ? 2 : 4;
-  t.chunks = per <= 4 ? 1 : (U + kChunkUnits - 1) / kChunkUnits;
-  if (t.chunks > 1) t.nv = 1;
-  return t;
-}
-
-struct Geo { int R, C, U, lg; };
-
-// the units one lane holds of one row: unit base + j * L + sub for j < NV (zeros where unit_ok says there is none)
-template <int VEC, int NV>
-struct Tile {
-  float v[NV][VEC];
-};
-
-template <int VEC>
-__device__ __forceinline__ void load_unit(const float* p, size_t unit, float (&d)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[unit];
-    d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-  } else {
-    d[0] = p[unit];
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_unit(float* p, size_t unit, const float (&d)[VEC]) {
-  if constexpr (VEC == 4) reinterpret_cast<float4*>(p)[unit] = make_float4(d[0], d[1], d[2], d[3]);
-  else p[unit] = d[0];
-}
-
-// keep bytes of one unit, one per element (nonzero = kept)
-template <int VEC>
-__device__ __forceinline__ void load_keep(const uint8_t* __restrict__ k, size_t unit, unsigned (&d)[VEC]) {
-  if constexpr (VEC == 4) {
-    const uint32_t w = reinterpret_cast<const uint32_t*>(k)[unit];
-    d[0] = w & 0xffu; d[1] = (w >> 8) & 0xffu; d[2] = (w >> 16) & 0xffu; d[3] = w >> 24;
-  } else {
-    d[0] = k[unit];
-  }
-}
-
-// where one lane stands in one visit of its workgroup
-struct Pos {
-  int L, sub, U;
-  size_t row, unit0;      // unit0: index of the row's first unit in the matrix
-  bool row_ok;
-};
-
-// whether unit j of the tile at ``base`` exists: inside the row, in a row of the matrix.  Recomputed wherever it is needed (a
-// compare) rather than kept: a kept flag per unit is a lane mask in a scalar register pair
-__device__ __forceinline__ bool unit_ok(const Pos& q, int base, int j) { return q.row_ok && base + j * q.L + q.sub < q.U; }
-
-template <int VEC, int NV>
-__device__ __forceinline__ Tile<VEC, NV> load_tile(const float* __restrict__ p, const Pos& q, int base) {
-  Tile<VEC, NV> t;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) t.v[j][e] = 0.f;
-    if (unit_ok(q, base, j)) load_unit<VEC>(p, q.unit0 + base + j * q.L + q.sub, t.v[j]);
-  }
-  return t;
-}
-
-// sum over the lanes that share a row (L a power of two, groups aligned to L: the butterfly never leaves the group)
-__device__ __forceinline__ float group_sum(float v, int L) {
-  for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using namespace bg::rowwise;
 
 // body(tile, its base) over what feeds a row's statistics: the lane's own registers, or on the chunked route every chunk of the row
 // from memory
@@ -155,31 +73,15 @@ __device__ __forceinline__ void write_partials(float (&acc)[NQ][NV][VEC], const 
   }
 }
 
-// (means are taken by true division by Cf: a row of equal values then has mean == the value and xh == 0 exactly)
-#define LN_POS_SETUP()                                                                                   \
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rpw = 64 >> g.lg;                          \
-  const int base = LOOP ? (int)blockIdx.y * 64 * NV : 0;                                                 \
-  const size_t groups = ((size_t)g.R + (size_t)rpw * kWaves - 1) / ((size_t)rpw * kWaves);               \
-  const float Cf = (float)g.C;                                                                           \
-  Pos q;                                                                                                \
-  q.L = LOOP ? 64 : 1 << g.lg; /* the chunked route always spreads a row over the whole wave: a constant stride */                                                                                      \
-  q.sub = lane & (q.L - 1);                                                                              \
-  q.U = g.U
-
-#define LN_ROW_SETUP()                                                      \
-  q.row = (rg * kWaves + wave) * (size_t)rpw + (size_t)(lane >> g.lg);      \
-  q.row_ok = q.row < (size_t)g.R;                                           \
-  q.unit0 = q.row * (size_t)g.U
-
 // a = Dropout(LeakyReLU(gamma * xh + beta)); saves mu, r
 template <int MODE, int VEC, int NV, bool LOOP>
 __global__ __launch_bounds__(kT) void ln_fwd_kernel(const float* __restrict__ z, float* __restrict__ a, Geo g,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                     float alpha, const uint8_t* __restrict__ keep, float kscale, size_t keep_rows,
                                                     float* __restrict__ mu, float* __restrict__ rs) {
-  LN_POS_SETUP();
+  ROWWISE_POS_SETUP();
   for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
-    LN_ROW_SETUP();
+    ROWWISE_ROW_SETUP();
     auto load = [&](int b) { return load_tile<VEC, NV>(z, q, b); };
     const Tile<VEC, NV> t = load(base);
     float s = 0.f;
@@ -247,7 +149,7 @@ struct ApplyArgs {
 // MODE 1, tangent:   vout = LeakyReLU' * gamma * M(zdot)
 template <int MODE, int VEC, int NV, bool LOOP>
 __global__ __launch_bounds__(kT) void ln_apply_kernel(ApplyArgs A, Geo g) {
-  LN_POS_SETUP();
+  ROWWISE_POS_SETUP();
   struct Pair { Tile<VEC, NV> z, u, y; };
   float acc[2][NV][VEC];
 #pragma unroll
@@ -257,7 +159,7 @@ __global__ __launch_bounds__(kT) void ln_apply_kernel(ApplyArgs A, Geo g) {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) acc[k][j][e] = 0.f;
   for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
-    LN_ROW_SETUP();
+    ROWWISE_ROW_SETUP();
     const float mean = q.row_ok ? A.mu[q.row] : 0.f, r = q.row_ok ? A.rs[q.row] : 0.f;
     const bool masked = MODE == 0 && A.keep != nullptr && q.row < A.keep_rows;
     // y: the vector M is applied to.  The factor f = LeakyReLU' [* Dropout'] of an element is formed wherever it is needed
@@ -354,7 +256,7 @@ __global__ __launch_bounds__(kT) void ln_source_kernel(const float* __restrict__
                                                        const float* __restrict__ z, float* __restrict__ s_out, Geo g,
                                                        const float* __restrict__ gamma, const float* __restrict__ mu,
                                                        const float* __restrict__ rs, float* __restrict__ partial) {
-  LN_POS_SETUP();
+  ROWWISE_POS_SETUP();
   struct Trio { Tile<VEC, NV> z, u, p, q; };      // p = gamma * u, q = zdot (both before centring)
   float acc[1][NV][VEC];
 #pragma unroll
@@ -362,7 +264,7 @@ __global__ __launch_bounds__(kT) void ln_source_kernel(const float* __restrict__
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[0][j][e] = 0.f;
   for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
-    LN_ROW_SETUP();
+    ROWWISE_ROW_SETUP();
     const float mean = q.row_ok ? mu[q.row] : 0.f, r = q.row_ok ? rs[q.row] : 0.f;
     auto load = [&](int b) {
       Trio t;
@@ -430,57 +332,13 @@ __global__ __launch_bounds__(kT) void ln_finish_kernel(const float* __restrict__
   const int idx = blockIdx.x * kWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (idx >= NQ * C) return;
   const int qn = idx / C, c = idx % C;
-  // a lane's loads are issued eight at a time and added in the loop's own order (misc.hip wave_sum_partials: the sum keeps its
-  // bits, and the lane waits for memory once per eight partial rows instead of once per row -- this launch is pure latency)
-  float s = 0.f;
-  int b = lane;
-  const size_t step = (size_t)64 * NQ * C;
-  const float* p = partial + ((size_t)b * NQ + qn) * C + c;
-  for (; b + 7 * 64 < nblk; b += 8 * 64, p += 8 * step) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = p[i * step];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[i];
-  }
-  if (b < nblk) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = b + i * 64 < nblk ? p[i * step] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (b + i * 64 < nblk) s += v[i];
-  }
+  float s = bg::lane_sum_partials(partial, nblk, NQ, qn, C, c);
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   if (lane == 0) {
     float* out = qn == 0 ? out0 : out1;
     out[c] = (beta != 0.f ? beta * out[c] : 0.f) + scale * s;
   }
 }
-
-inline Geo geo_for(int R, int C, const Route& t) { return Geo{R, C, C / t.vec, t.lg}; }
-
-inline dim3 grid_for(int R, const Route& t) {
-  const size_t rows_wg = (size_t)kWaves * (64 >> t.lg);
-  const size_t groups = ((size_t)R + rows_wg - 1) / rows_wg;
-  return dim3((unsigned)std::min<size_t>(groups, kMaxBlocks), (unsigned)t.chunks);
-}
-
-#define LN_LAUNCH(KERN, MODE, t, grid, s, ...)                                                                  \
-  do {                                                                                                          \
-    if (t.chunks > 1) {                                                                                         \
-      if (t.vec == 4) bg::launch(KERN<MODE, 4, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else bg::launch(KERN<MODE, 1, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                               \
-    } else if (t.vec == 4) {                                                                                    \
-      if (t.nv == 1) bg::launch(KERN<MODE, 4, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else if (t.nv == 2) bg::launch(KERN<MODE, 4, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
-      else bg::launch(KERN<MODE, 4, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
-    } else {                                                                                                    \
-      if (t.nv == 1) bg::launch(KERN<MODE, 1, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else if (t.nv == 2) bg::launch(KERN<MODE, 1, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
-      else bg::launch(KERN<MODE, 1, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
-    }                                                                                                           \
-  } while (0)
 
 inline bool al(const void* p) { return bg::aligned16(p); }      // NULL counts as aligned
 
@@ -522,7 +380,11 @@ int bg_ln_fwd_f32(const float* z, float* a, int R, int C, const float* gamma, co
   const size_t keep_rows = keep_elems ? keep_elems / (size_t)C : (size_t)R;
   bg::Launch L(stream, "ln_fwd", 0, (8.0 + (keep ? 1.0 : 0.0)) * R * C + 8.0 * R);
   const dim3 grid = grid_for(R, t);
-  LN_LAUNCH(ln_fwd_kernel, 0, t, grid, L.s, z, a, geo_for(R, C, t), gamma, beta, eps, lrelu_alpha, keep, keep_scale, keep_rows, mu, r);
+  for_route(t, [&](auto lanes) {
+    using Rt = decltype(lanes);
+    bg::launch(ln_fwd_kernel<0, Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, z, a, geo_for(R, C, t), gamma, beta, eps, lrelu_alpha, keep,
+               keep_scale, keep_rows, mu, r);
+  });
   return L.done("ln_fwd_kernel");
 }
 
@@ -554,7 +416,10 @@ int bg_ln_bwd_f32(const float* g, const float* z, float* dz, int R, int C, const
   A.dw_rows = dw_rows > 0 ? (size_t)dw_rows : (size_t)R;
   {
     bg::Launch L(stream, "ln_bwd", 0, (12.0 + (keep ? 1.0 : 0.0) + (addend ? 4.0 : 0.0)) * R * C + (u_out ? 4.0 * u_rows * C : 0.0) + 8.0 * R);
-    LN_LAUNCH(ln_apply_kernel, 0, t, grid, L.s, A, geo_for(R, C, t));
+    for_route(t, [&](auto lanes) {
+      using Rt = decltype(lanes);
+      bg::launch(ln_apply_kernel<0, Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, A, geo_for(R, C, t));
+    });
     const int rc = L.done("ln_apply_kernel");
     if (rc || !dgamma) return rc;
   }
@@ -577,7 +442,10 @@ int bg_ln_tangent_f32(const float* zdot, const float* z, float* vout, int R, int
   A.partial = nullptr; A.dw_rows = 0;
   bg::Launch L(stream, "ln_tangent", 0, 12.0 * R * C + 8.0 * R);
   const dim3 grid = grid_for(R, t);
-  LN_LAUNCH(ln_apply_kernel, 1, t, grid, L.s, A, geo_for(R, C, t));
+  for_route(t, [&](auto lanes) {
+    using Rt = decltype(lanes);
+    bg::launch(ln_apply_kernel<1, Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, A, geo_for(R, C, t));
+  });
   return L.done("ln_apply_kernel");
 }
 
@@ -594,7 +462,10 @@ int bg_ln_gp_source_f32(const float* u, const float* zdot, const float* z, float
   float* partial = static_cast<float*>(ws_d);
   {
     bg::Launch L(stream, "ln_gp_source", 0, 16.0 * R * C + 8.0 * R);
-    LN_LAUNCH(ln_source_kernel, 0, t, grid, L.s, u, zdot, z, s, geo_for(R, C, t), gamma, mu, r, partial);
+    for_route(t, [&](auto lanes) {
+      using Rt = decltype(lanes);
+      bg::launch(ln_source_kernel<0, Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, u, zdot, z, s, geo_for(R, C, t), gamma, mu, r, partial);
+    });
     const int rc = L.done("ln_source_kernel");
     if (rc) return rc;
   }

@@ -20,6 +20,7 @@
 // The backward needs no such wait: its scalar q is a sum over the G * P floats of channel C of the incoming gradient, which every
 // workgroup of the group adds up for itself in the same order; one launch on either route, nothing in LDS but the waves' partials.
 #include "common.h"
+#include "reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -64,36 +65,13 @@ __device__ __forceinline__ void st(float* p, const float (&v)[4]) {
   }
 }
 
-// f1(o) for the scalar head and tail, f4(o) for every float4 of the flat range [0, n) that starts at byte address ``addr`` (4-byte
-// aligned): o of an f4 call is 16-byte aligned in memory.  The float4s are dealt to the K workgroups of the group in contiguous
-// runs (k-th of K); the head goes with the first run, the tail with the last.
-template <class F4, class F1>
-__device__ __forceinline__ void sweep(uintptr_t addr, int n, int k, int K, F4 f4, F1 f1) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  int head = (int)(((16u - (unsigned)(addr & 15u)) & 15u) >> 2);
-  head = head < n ? head : n;
-  const int nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
-  const int per = (nvec + K - 1) / K, vlo = k * per, vhi = vlo + per < nvec ? vlo + per : nvec;
-  if (k == 0 && tid < head) f1(tid);
-  for (int v = vlo + tid; v < vhi; v += T) f4(head + 4 * v);
-  if (k == K - 1 && tid < n - tail0) f1(tail0 + tid);
-}
+using bg::block_sum;      // reduce.h: the workgroup's sum; red may still be read from the previous group, hence its first barrier
+using bg::sweep;          // reduce.h: scalar head, float4 runs dealt to the K workgroups of the group, scalar tail
 
 // whether every one of the pointers is 16-byte aligned
 template <class... P>
 __device__ __forceinline__ bool all_aligned(P... p) {
   return (((reinterpret_cast<uintptr_t>(p)) | ...) & 15u) == 0;
-}
-
-// sum over the workgroup in a fixed order; every thread gets it
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                                       // red may still be read from the previous group
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = red[0];
-  for (int w = 1, nw = blockDim.x >> 6; w < nw; ++w) s += red[w];
-  return s;
 }
 
 // the group's output range: out[o] = img[o - o / (C + 1)] in channels [0, C), ``val`` in channel C

@@ -2,6 +2,7 @@
 // pointwise GP helpers, losses, Adam, RNG.  Each replaces the TF op named beside it
 // (SURVEY.md 8a rows T4-T12); all are bandwidth-bound, written as coalesced grid-stride kernels.
 #include "common.h"
+#include "reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -11,9 +12,7 @@ __device__ inline bool bg_aligned16(const void* p) { return (reinterpret_cast<ui
 
 constexpr int kT = 256;
 
-inline unsigned grid_for(size_t n, int per_thread = 1) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(bg::cdiv(n, (size_t)kT * per_thread), 256 * 8));
-}
+inline unsigned grid_for(size_t n, int per_thread = 1) { return bg::grid_cap(n, kT, per_thread); }
 
 // ---------------------------------------------------------------- Dense (layers.Dense, demo_celeba.py:55,124)
 __global__ __launch_bounds__(kT) void gemm_naive_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
@@ -290,29 +289,9 @@ __global__ __launch_bounds__(kT) void bn_bwd_flat_kernel(const float* __restrict
   }, M, C, partial);
 }
 
-// one wave per channel sums the per-block partials: partial[(b*NQ + q)*C + c]
-// (the loads of a lane are issued eight at a time and added in the loop's own order: the sum keeps its bits, and a lane waits for
-// memory once per eight partial rows instead of once per row -- these finals are pure latency, 4-7 us for microseconds of work)
+// one wave per channel sums the per-block partials: partial[(b*NQ + q)*C + c]; every lane gets the sum
 __device__ inline float wave_sum_partials(const float* __restrict__ partial, int nblk, int NQ, int q, int C, int c) {
-  float s = 0.f;
-  int b = threadIdx.x & 63;
-  const size_t step = (size_t)64 * NQ * C;
-  const float* p = partial + ((size_t)b * NQ + q) * C + c;
-  for (; b + 7 * 64 < nblk; b += 8 * 64, p += 8 * step) {
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = p[i * step];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[i];
-  }
-  if (b < nblk) {                               // the last, partial batch (all of it when nblk < 512): predicated, still one wait
-    float v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = b + i * 64 < nblk ? p[i * step] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (b + i * 64 < nblk) s += v[i];
-  }
+  float s = bg::lane_sum_partials(partial, nblk, NQ, q, C, c);
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   return __shfl(s, 0, 64);
 }
@@ -697,6 +676,8 @@ __global__ __launch_bounds__(kT) void scale_kernel(float* x, float v, size_t n) 
 }
 
 // ---------------------------------------------------------------- losses (single workgroup; B is small)
+// Not reduce.h's block_sum, and not to be replaced by it: this one folds a wave with __shfl_down and adds the four waves as one
+// expression; the loss values' bits depend on both.
 __device__ inline float block_sum(float v, float* red) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   __syncthreads();

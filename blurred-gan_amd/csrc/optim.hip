@@ -12,10 +12,6 @@ namespace {
 
 constexpr int kT = 256;
 
-inline unsigned grid_for4(size_t n) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(bg::cdiv(n, (size_t)kT * 4), 256 * 8));
-}
-
 // The sweep every variant shares.  f(theta, s1, s2, s3, g) updates one element in place; slot streams the variant does not use
 // (U* = false) are neither loaded nor stored, so their pointers may be null.
 template <bool U1, bool U2, bool U3, class F>
@@ -145,7 +141,7 @@ int bg_sgd_f32(float* theta, float* a, const float* g, size_t n, float lr, float
   bg::Launch L(stream, !mom ? "sgd" : nesterov ? "sgd_nesterov" : "sgd_momentum", 0, (mom ? 20.0 : 12.0) * n);
   const int slot = bg::take_bind(BG_BIND_OPT_LR);          // step program: lr re-read from a slot before every replay
   auto k = !mom ? sgd_kernel<false, false> : nesterov ? sgd_kernel<true, true> : sgd_kernel<true, false>;
-  bg::launch(k, dim3(grid_for4(n)), dim3(kT), 0, L.s, theta, mom ? a : nullptr, g, n, lr, momentum);
+  bg::launch(k, dim3(bg::grid_cap(n, kT, 4)), dim3(kT), 0, L.s, theta, mom ? a : nullptr, g, n, lr, momentum);
   bg::bind_last(4, bg::BIND_F32_FROM_F64, slot);
   return L.done("sgd_kernel");
 }
@@ -165,7 +161,7 @@ int bg_rmsprop_f32(float* theta, float* r, float* p, float* mg, const float* g, 
   const int slot = bg::take_bind(BG_BIND_OPT_LR);
   auto k = mom ? (cen ? rmsprop_kernel<true, true> : rmsprop_kernel<true, false>)
                : (cen ? rmsprop_kernel<false, true> : rmsprop_kernel<false, false>);
-  bg::launch(k, dim3(grid_for4(n)), dim3(kT), 0, L.s, theta, r, mom ? p : nullptr, cen ? mg : nullptr, g, n, lr, rho, momentum, eps);
+  bg::launch(k, dim3(bg::grid_cap(n, kT, 4)), dim3(kT), 0, L.s, theta, r, mom ? p : nullptr, cen ? mg : nullptr, g, n, lr, rho, momentum, eps);
   bg::bind_last(6, bg::BIND_F32_FROM_F64, slot);
   return L.done("rmsprop_kernel");
 }
@@ -177,7 +173,7 @@ int bg_adam_amsgrad_f32(float* theta, float* m, float* v, float* vhat, const flo
   BG_REQUIRE(al(theta) && al(m) && al(v) && al(vhat) && al(g), BG_ERR_BAD_ALIGNMENT, "bg_adam_amsgrad_f32: pointers must be 16-byte aligned");
   bg::Launch L(stream, "adam_amsgrad", 0, 36.0 * n);
   const int slot = bg::take_bind(BG_BIND_OPT_LR);
-  bg::launch(adam_amsgrad_kernel, dim3(grid_for4(n)), dim3(kT), 0, L.s, theta, m, v, vhat, g, n, lr_t, b1, b2, eps);
+  bg::launch(adam_amsgrad_kernel, dim3(bg::grid_cap(n, kT, 4)), dim3(kT), 0, L.s, theta, m, v, vhat, g, n, lr_t, b1, b2, eps);
   bg::bind_last(6, bg::BIND_F32_FROM_F64, slot);
   return L.done("adam_amsgrad_kernel");
 }
@@ -190,7 +186,7 @@ int bg_ema_f32(float* avg, const float* theta, size_t n, float* avg2, const floa
              "bg_ema_f32: pointers must be 16-byte aligned");
   bg::Launch L(stream, "ema", 0, 12.0 * (double)(n + n2));
   const int slot = bg::take_bind(BG_BIND_EMA_W);           // step program: w re-read from a slot before every replay
-  bg::launch(ema_kernel, dim3(grid_for4(n)), dim3(kT), 0, L.s, avg, theta, n, n2 ? avg2 : nullptr, n2 ? theta2 : nullptr, n2, w);
+  bg::launch(ema_kernel, dim3(bg::grid_cap(n, kT, 4)), dim3(kT), 0, L.s, avg, theta, n, n2 ? avg2 : nullptr, n2 ? theta2 : nullptr, n2, w);
   bg::bind_last(6, bg::BIND_F32_FROM_F64, slot);
   return L.done("ema_kernel");
 }

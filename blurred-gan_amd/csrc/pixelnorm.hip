@@ -7,112 +7,26 @@
 // a backward follows),  y = a * r;  the Jacobian of a -> y is r * (I - y y^T / C), and r > 0 gives sign(y) = sign(x): the backward
 // reads LeakyReLU's branch from the stored output and never sees x.
 //
-// Routes (bg_pixelnorm_route reports the ones a C takes) follow csrc/layernorm.hip's.  A row is read in units of one float4
-// (C % 4 == 0 and every matrix of the call 16-byte aligned) or one float (anything else, a misaligned view included: no call is
-// refused for its alignment): U = C / 4 or C units.  L = the power of two >= U, at most 64, lanes share a row, so a wave holds
-// 64 / L rows; with U > 64 each lane keeps 2 or 4 units (U <= 128, U <= 256).  Up to there a row is read ONCE and stays in
-// registers between its sum and its use.  Beyond (U > 256: C > 1024, or C > 256 by single floats) the row is cut into chunks of 64
-// units, one per lane, along gridDim.y: a workgroup sweeps the whole row from memory for the sum (the re-read hits L2) and keeps
-// only its own chunk in registers.  A workgroup is 4 waves = 4 * 64 / L rows per visit, in a grid-stride loop over at most 1024
-// workgroups.  A row's sum is each lane's units in index order, then a fixed butterfly over the lanes that share it.
+// Routes (bg_pixelnorm_route reports the ones a C takes): csrc/rowwise.h's, with float4 units only where C % 4 == 0 AND every
+// matrix of the call is 16-byte aligned; anything else, a misaligned view included, goes by single floats: no call is refused for
+// its alignment.  Up to 256 units a row is read ONCE and stays in registers between its sum and its use, so the output may alias
+// the source it replaces there (x and the incoming gradient carry no __restrict__).
 #include "common.h"
-#include <algorithm>
+#include "rowwise.h"
 
 namespace {
 
-constexpr int kT = 256, kWaves = kT / 64, kMaxBlocks = 1024, kChunkUnits = 64;
-
-struct Route { int vec, lg, nv, chunks; };
-
-inline Route route_for(int C, bool aligned = true) {
-  Route t;
-  t.vec = C % 4 == 0 && aligned ? 4 : 1;
-  const int U = C / t.vec;
-  t.lg = 0;
-  while ((1 << t.lg) < U && t.lg < 6) ++t.lg;
-  const int per = (U + 63) / 64;
-  t.nv = per <= 1 ? 1 : per <= 2 ? 2 : 4;
-  t.chunks = per <= 4 ? 1 : (U + kChunkUnits - 1) / kChunkUnits;
-  if (t.chunks > 1) t.nv = 1;
-  return t;
-}
-
-struct Geo { int R, C, U, lg; };
-
-// the units one lane holds of one row: unit base + j * L + sub for j < NV (zeros where unit_ok says there is none)
-template <int VEC, int NV>
-struct Tile {
-  float v[NV][VEC];
-};
-
-template <int VEC>
-__device__ __forceinline__ void load_unit(const float* p, size_t unit, float (&d)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[unit];
-    d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
-  } else {
-    d[0] = p[unit];
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_unit(float* p, size_t unit, const float (&d)[VEC]) {
-  if constexpr (VEC == 4) reinterpret_cast<float4*>(p)[unit] = make_float4(d[0], d[1], d[2], d[3]);
-  else p[unit] = d[0];
-}
-
-// where one lane stands in one visit of its workgroup
-struct Pos {
-  int L, sub, U;
-  size_t row, unit0;      // unit0: index of the row's first unit in the matrix
-  bool row_ok;
-};
-
-__device__ __forceinline__ bool unit_ok(const Pos& q, int base, int j) { return q.row_ok && base + j * q.L + q.sub < q.U; }
-
-// no __restrict__ on the sources: the output may alias one of them on the register routes
-template <int VEC, int NV>
-__device__ __forceinline__ Tile<VEC, NV> load_tile(const float* p, const Pos& q, int base) {
-  Tile<VEC, NV> t;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) t.v[j][e] = 0.f;
-    if (unit_ok(q, base, j)) load_unit<VEC>(p, q.unit0 + base + j * q.L + q.sub, t.v[j]);
-  }
-  return t;
-}
-
-// sum over the lanes that share a row (L a power of two, groups aligned to L: the butterfly never leaves the group)
-__device__ __forceinline__ float group_sum(float v, int L) {
-  for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using namespace bg::rowwise;
 
 __device__ __forceinline__ float lrelu(float x, float alpha) { return x > 0.f ? x : alpha * x; }
-
-#define PN_POS_SETUP()                                                                                   \
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rpw = 64 >> g.lg;                          \
-  const int base = LOOP ? (int)blockIdx.y * 64 * NV : 0;                                                 \
-  const size_t groups = ((size_t)g.R + (size_t)rpw * kWaves - 1) / ((size_t)rpw * kWaves);               \
-  const float Cf = (float)g.C;                                                                           \
-  Pos q;                                                                                                \
-  q.L = LOOP ? 64 : 1 << g.lg; /* the chunked route spreads a row over the whole wave */                 \
-  q.sub = lane & (q.L - 1);                                                                              \
-  q.U = g.U
-
-#define PN_ROW_SETUP()                                                      \
-  q.row = (rg * kWaves + wave) * (size_t)rpw + (size_t)(lane >> g.lg);      \
-  q.row_ok = q.row < (size_t)g.R;                                           \
-  q.unit0 = q.row * (size_t)g.U
 
 // y = a * r with a = LeakyReLU(x), r = 1 / sqrt(mean(a^2) + eps); saves r where rs != NULL.  (A unit that does not exist is zeros
 // and adds nothing to the sum of squares.)
 template <int VEC, int NV, bool LOOP>
 __global__ __launch_bounds__(kT) void pn_fwd_kernel(const float* x, float* y, Geo g, float eps, float alpha, float* __restrict__ rs) {
-  PN_POS_SETUP();
+  ROWWISE_POS_SETUP();
   for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
-    PN_ROW_SETUP();
+    ROWWISE_ROW_SETUP();
     Tile<VEC, NV> t = load_tile<VEC, NV>(x, q, base);
     float s = 0.f;
     if constexpr (!LOOP) {
@@ -156,9 +70,9 @@ __global__ __launch_bounds__(kT) void pn_fwd_kernel(const float* x, float* y, Ge
 template <int VEC, int NV, bool LOOP>
 __global__ __launch_bounds__(kT) void pn_bwd_kernel(const float* gr, const float* __restrict__ y, const float* __restrict__ rs, float* dz,
                                                     Geo g, float alpha) {
-  PN_POS_SETUP();
+  ROWWISE_POS_SETUP();
   for (size_t rg = blockIdx.x; rg < groups; rg += gridDim.x) {
-    PN_ROW_SETUP();
+    ROWWISE_ROW_SETUP();
     const float r = q.row_ok ? rs[q.row] : 0.f;
     const Tile<VEC, NV> tg = load_tile<VEC, NV>(gr, q, base), ty = load_tile<VEC, NV>(y, q, base);
     float s = 0.f;
@@ -191,30 +105,6 @@ __global__ __launch_bounds__(kT) void pn_bwd_kernel(const float* gr, const float
   }
 }
 
-inline Geo geo_for(int R, int C, const Route& t) { return Geo{R, C, C / t.vec, t.lg}; }
-
-inline dim3 grid_for(int R, const Route& t) {
-  const size_t rows_wg = (size_t)kWaves * (64 >> t.lg);
-  const size_t groups = ((size_t)R + rows_wg - 1) / rows_wg;
-  return dim3((unsigned)std::min<size_t>(groups, kMaxBlocks), (unsigned)t.chunks);
-}
-
-#define PN_LAUNCH(KERN, t, grid, s, ...)                                                                  \
-  do {                                                                                                    \
-    if (t.chunks > 1) {                                                                                   \
-      if (t.vec == 4) bg::launch(KERN<4, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else bg::launch(KERN<1, 1, true>, grid, dim3(kT), 0, s, __VA_ARGS__);                               \
-    } else if (t.vec == 4) {                                                                              \
-      if (t.nv == 1) bg::launch(KERN<4, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else if (t.nv == 2) bg::launch(KERN<4, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
-      else bg::launch(KERN<4, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
-    } else {                                                                                              \
-      if (t.nv == 1) bg::launch(KERN<1, 1, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                    \
-      else if (t.nv == 2) bg::launch(KERN<1, 2, false>, grid, dim3(kT), 0, s, __VA_ARGS__);               \
-      else bg::launch(KERN<1, 4, false>, grid, dim3(kT), 0, s, __VA_ARGS__);                              \
-    }                                                                                                     \
-  } while (0)
-
 inline bool al(const void* p) { return bg::aligned16(p); }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }      // NULL counts as aligned
 
@@ -244,7 +134,10 @@ int bg_pixelnorm_fwd_f32(const float* x, float* y, float* r, int R, int C, float
              "bg_pixelnorm_fwd_f32: y may alias x on the register routes only (C=%d is swept in %d chunks)", C, t.chunks);
   bg::Launch L(stream, "pixelnorm_fwd", 0, 8.0 * R * C + (r ? 4.0 * R : 0.0));
   const dim3 grid = grid_for(R, t);
-  PN_LAUNCH(pn_fwd_kernel, t, grid, L.s, x, y, geo_for(R, C, t), eps, lrelu_alpha, r);
+  for_route(t, [&](auto lanes) {
+    using Rt = decltype(lanes);
+    bg::launch(pn_fwd_kernel<Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, x, y, geo_for(R, C, t), eps, lrelu_alpha, r);
+  });
   return L.done("pn_fwd_kernel");
 }
 
@@ -258,7 +151,10 @@ int bg_pixelnorm_bwd_f32(const float* g, const float* y, const float* r, float* 
              "bg_pixelnorm_bwd_f32: dz may alias g on the register routes only (C=%d is swept in %d chunks)", C, t.chunks);
   bg::Launch L(stream, "pixelnorm_bwd", 0, 12.0 * R * C + 4.0 * R);
   const dim3 grid = grid_for(R, t);
-  PN_LAUNCH(pn_bwd_kernel, t, grid, L.s, g, y, r, dz, geo_for(R, C, t), lrelu_alpha);
+  for_route(t, [&](auto lanes) {
+    using Rt = decltype(lanes);
+    bg::launch(pn_bwd_kernel<Rt::VEC, Rt::NV, Rt::LOOP>, grid, dim3(kT), 0, L.s, g, y, r, dz, geo_for(R, C, t), lrelu_alpha);
+  });
   return L.done("pn_bwd_kernel");
 }
 

@@ -12,8 +12,6 @@ namespace {
 
 constexpr int kT = 256;
 
-inline unsigned grid_cap(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>(bg::cdiv(n, (size_t)kT), 256 * 8)); }
-
 // bg_mul_grad_f32's factor (misc.hip mul_grad_kernel), operation for operation
 __device__ inline float grad_factor(float r, bool has_keep, unsigned k, float alpha, float gscale) {
   float f = r > 0.f ? 1.f : alpha;
@@ -126,7 +124,7 @@ int bg_upsample2x_nhwc_f32(const float* x, float* y, int B, int H, int W, int C,
              "bg_upsample2x_nhwc_f32: pointers must be 16-byte aligned when C %% 4 == 0");
   const size_t n = (size_t)B * H * W * C, units = v4 ? n / 4 : n, CU = v4 ? C / 4 : C;
   bg::Launch L(stream, ref ? "upsample2x_mul_grad" : "upsample2x", 0, (20.0 + (ref ? 16.0 : 0.0) + (keep ? 4.0 : 0.0)) * n);
-  const dim3 grid(grid_cap(units)), block(kT);
+  const dim3 grid(bg::grid_cap(units, kT)), block(kT);
   if (v4) {
     const float4* x4 = reinterpret_cast<const float4*>(x);
     const float4* r4 = reinterpret_cast<const float4*>(ref);
@@ -153,7 +151,7 @@ int bg_pool2x_sum_nhwc_f32(const float* x, float* y, int B, int H, int W, int C,
              "bg_pool2x_sum_nhwc_f32: pointers must be 16-byte aligned when C %% 4 == 0");
   const size_t n = (size_t)B * H * W * C, units = v4 ? n / 4 : n, CU = v4 ? C / 4 : C;
   bg::Launch L(stream, "pool2x_sum", 0, 20.0 * n);
-  const dim3 grid(grid_cap(units)), block(kT);
+  const dim3 grid(bg::grid_cap(units, kT)), block(kT);
   if (v4)
     bg::launch(pool2x_sum_v4_kernel, grid, block, 0, L.s, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), units, (size_t)H,
                (size_t)W, CU, scale);

@@ -71,6 +71,8 @@ __device__ inline float wave_sum(float x) {
 }
 
 // Sum over the workgroup's 256 threads in a fixed order; every thread gets it.  red: 4 floats of LDS.
+// Not reduce.h's block_sum, and not to be replaced by it: the butterfly runs in ascending offsets, the waves add as
+// ((r0 + r1) + r2) + r3, and the second barrier FOLLOWS the read because the callers write red again at once.
 __device__ inline float block_sum(float x, float* red) {
   x = wave_sum(x);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;

@@ -18,12 +18,12 @@ import numpy as np
 F32, F64 = np.float32, np.float64
 ALPHA, KEEP_SCALE = 0.25, 2.0
 KEEP_BYTES = (0, 1, 2, 0x80, 0xFF)
-K_T, K_WAVES, K_MAX_BLOCKS, K_CHUNK_UNITS = 256, 4, 1024, 64          # layernorm.hip: kT, kWaves, kMaxBlocks, kChunkUnits
+K_T, K_WAVES, K_MAX_BLOCKS, K_CHUNK_UNITS = 256, 4, 1024, 64          # rowwise.h: kT, kWaves, kMaxBlocks, kChunkUnits
 
 
 # ------------------------------------------------------------------ the routes, restated
 def route_for(C):
-    """layernorm.hip route_for (the lines from ``t.vec = C % 4 == 0 ? 4 : 1`` to ``if (t.chunks > 1) t.nv = 1``)."""
+    """rowwise.h route_for with aligned = true (the lines from ``t.vec = C % 4 == 0 && aligned ? 4 : 1`` to ``if (t.chunks > 1) t.nv = 1``)."""
     vec = 4 if C % 4 == 0 else 1
     U = C // vec
     lg = 0
@@ -38,7 +38,7 @@ def route_for(C):
 
 
 def rows_per_workgroup(C):
-    """grid_for's ``rows_wg = kWaves * (64 >> t.lg)`` (LN_POS_SETUP's rpw * kWaves)."""
+    """grid_for's ``rows_wg = kWaves * (64 >> t.lg)`` (ROWWISE_POS_SETUP's rpw * kWaves)."""
     return K_WAVES * (64 // route_for(C)["lanes"])
 
 

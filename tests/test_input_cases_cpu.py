@@ -1,5 +1,5 @@
 """What the case list of the input pipeline's kernel tests (tests/input_cases.py) reaches, proved from arithmetic on the list alone: no
-GPU, no kernel.  The launch constants the list restates are checked against the text of csrc/input.hip and csrc/misc.hip, so the list
+GPU, no kernel.  The launch constants the list restates are checked against the text of csrc/input.hip, csrc/misc.hip and the grid cap both take from csrc/common.h, so the list
 cannot drift from the launches unnoticed; the two oracles alone decide that no geometry needs a yardstick wider than the dense kernel's
 atol."""
 import os
@@ -57,8 +57,12 @@ def test_the_restated_launch_constants_are_the_sources():
     for path in ("input.hip", "misc.hip"):
         text = open(os.path.join(CSRC, path)).read()
         assert re.search(r"constexpr int kT = (\d+);", text).group(1) == str(IC.THREADS), path
-        grid = re.search(r"inline unsigned grid_for\(size_t n[^)]*\) \{\s*return .*?, (\d+) \* (\d+)\)\);", text, flags=re.S)
-        assert grid and int(grid.group(1)) * int(grid.group(2)) == IC.MAX_BLOCKS and grid.group(0).count("kT") == 1, path
+        # either file's grid_for is bg::grid_cap (common.h) with its own kT: one workgroup per kT units, at most MAX_BLOCKS of them
+        assert re.search(r"inline unsigned grid_for\(size_t n[^)]*\) \{ return bg::grid_cap\(n, kT(, per_thread)?\); \}", text), path
+    grid = re.search(r"inline unsigned grid_cap\(size_t n, int threads, int per_thread = 1\) \{\s*return [^;]*?, (\d+) \* (\d+)\)\);",
+                     open(os.path.join(CSRC, "common.h")).read())
+    assert grid and int(grid.group(1)) * int(grid.group(2)) == IC.MAX_BLOCKS
+    assert grid.group(0).count("threads") == 2 and "cdiv(n, (size_t)threads * per_thread)" in grid.group(0)
     text = open(os.path.join(CSRC, "input.hip")).read()
     # the channel counts of the four-pixel kernel, the units its grid is sized by, and the dense kernel's: one float per lane
     assert tuple(int(c) for c in re.findall(r"case (\d+): bg::launch\(u8_gather_resize_vec_kernel<\1>", text)) == IC.VEC_C

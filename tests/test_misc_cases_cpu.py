@@ -35,13 +35,18 @@ def _holds(shape, facts):
 
 
 def test_predicates_restate_the_source():
-    """The lines of misc.hip the predicates are restated from are still there, letter for letter."""
+    """The lines of misc.hip the predicates are restated from are still there, letter for letter; the grid cap and the fold of
+    partial rows that it shares with other files, in the headers it takes them from (misc.hip calls them with its own kT)."""
     src = open(SRC).read()
-    for line in ["std::min<size_t>(bg::cdiv(n, (size_t)kT * per_thread), 256 * 8)", "constexpr int kT = 256;",
+    csrc = os.path.dirname(SRC)
+    assert "std::min<size_t>(cdiv(n, (size_t)threads * per_thread), 256 * 8)" in open(os.path.join(csrc, "common.h")).read()
+    assert "for (; b + 7 * 64 < nblk; b += 8 * 64, p += 8 * step) {" in open(os.path.join(csrc, "reduce.h")).read()
+    for line in ["inline unsigned grid_for(size_t n, int per_thread = 1) { return bg::grid_cap(n, kT, per_thread); }",
+                 "float s = bg::lane_sum_partials(partial, nblk, NQ, q, C, c);", "constexpr int kT = 256;",
                  "return C >= 4 && C <= 1024 && (C & (C - 1)) == 0 && M >= 64;", "std::min<size_t>({cap, total4 / (kT * 8), (size_t)M})",
                  "(size_t)atoi(getenv(\"BG_FLAT_BLOCKS\")) : 512;", "std::max(1, std::min(kColBlocks, M / 16))", "constexpr int kColBlocks = 256;",
                  "if (N == 1 && !transA && K >= 64) {", "if (N == 1 && transA && K >= 64) {", "if ((size_t)M * N >= 4096 && K >= 8) {",
-                 "for (; b + 7 * 64 < nblk; b += 8 * 64, p += 8 * step) {", "for (; q4 + (size_t)(U - 1) * kT < total4; q4 += (size_t)U * kT) {",
+                 "for (; q4 + (size_t)(U - 1) * kT < total4; q4 += (size_t)U * kT) {",
                  "for (; q + stride < total4; q += 2 * stride) {", "if ((stride * 4u) % (unsigned)C == 0u) {", "flat_reduce<1, 8>(",
                  "flat_reduce<2, 8>(", "flat_reduce<2, 4>(", "dim3(grid_for(n, vec ? 4 : 1))"]:
         assert line in src, line
