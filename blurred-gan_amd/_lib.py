@@ -97,6 +97,10 @@ SIGNATURES = {
     "bg_spectral_power_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _z, _p]),
     "bg_spectral_scale_f32": (_i, [_p, _p, _p, _p, _p, _i, _p]),
     "bg_spectral_grad_f32": (_i, [_p, _p, _p, _p, _p, _i, _p, _z, _p]),
+    "bg_eqlr_plan": (_i, [_i, _i, _i] + [C.POINTER(_i)] * 4),
+    "bg_eqlr_check_table": (_i, [_p, _i, _z, _z]),
+    "bg_eqlr_scale_f32": (_i, [_p, _z, _p, _z, _p, _p, _i, _p]),
+    "bg_eqlr_grad_f32": (_i, [_p, _z, _p, _p, _i, _p]),
     "bg_lerp_f32":(_i, [_p, _p, _p, _p, _i, _i, _p]),
     "bg_row_norm_f32": (_i, [_p, _p, _i, _i, _p]),
     "bg_gp_seed_f32": (_i, [_p, _p, _f, _p, _i, _i, _p]),
@@ -157,6 +161,7 @@ COMM_ID_BYTES = 128
 PIXELNORM_ROUTE_INTS = 8       # include/bgan.h BG_PIXELNORM_ROUTE_INTS
 MBSTD_PLAN_INTS = 12          # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
+EQLR_DESC_INTS = 12            # include/bgan.h BG_EQLR_DESC_INTS
 LOSS_WASSERSTEIN, LOSS_HINGE, LOSS_NONSATURATING = 0, 1, 2      # include/bgan.h bg_gan_loss
 BIND_ADAM_LR, BIND_RNG_OFFSET, BIND_OPT_LR, BIND_EMA_W = 1, 2, 3, 4      # include/bgan.h BG_BIND_*
 

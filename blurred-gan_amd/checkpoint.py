@@ -36,6 +36,12 @@ def _json_default(x):
 _CKPT_NAME = re.compile(r"^ckpt-\d+\.npz$")
 
 
+def _eqlr_signature(model):
+    """The fp32 coefficients of the model's EqualizedLearningRate layers, in layer order ([]: a plain model).  The wrapper adds no
+    variable and changes no shape, so only this list tells a checkpoint of raw N(0, 1) kernels from one of plain weights."""
+    return [float(np.float32(l.coefficient)) for l in model.net().eqlr_layers]
+
+
 class CheckpointManager:
     def __init__(self, gan, directory, max_to_keep=5, keep_checkpoint_every_n_hours=None):
         self.gan, self.directory = gan, directory
@@ -97,6 +103,7 @@ class CheckpointManager:
             lr = opt.learning_rate
             d[f"{tag}_opt_lr"] = np.float64(lr if not callable(lr) else np.nan)      # a schedule lives in the config
             d[f"{tag}_rng_offset"] = np.int64(int(model.net().rng_offset))        # dropout-mask stream of this network
+            d[f"{tag}_eqlr"] = np.asarray(_eqlr_signature(model), dtype=np.float32)
         if getattr(g, "generator_ema", None) is not None:
             st = g.generator_ema.store
             d["g_ema_theta"] = st.theta.cpu().numpy()
@@ -134,6 +141,12 @@ class CheckpointManager:
     def restore(self, path):
         g = self.gan
         d = np.load(path)
+        for tag, model in (("g", g.generator), ("d", g.discriminator)):        # before anything of either model is overwritten
+            saved_eqlr = [float(c) for c in d[f"{tag}_eqlr"]] if f"{tag}_eqlr" in d.files else []      # older files: a plain model
+            if saved_eqlr != _eqlr_signature(model):
+                raise ValueError(f"{path}: the {'generator' if tag == 'g' else 'discriminator'} was saved with the equalised-learning-rate "
+                                 f"coefficients {saved_eqlr}, the model's wrapped layers have {_eqlr_signature(model)}: the raw kernels of "
+                                 "one are not the weights of the other (an empty list is a plain model)")
         g.n_img.assign(int(d["n_img"]))
         g.n_batches.assign(int(d["n_batches"]))
         if "rng_off" in d.files:

@@ -15,7 +15,7 @@ from __future__ import annotations
 import copy
 import numbers
 
-from .layers import Sequential
+from .layers import EqualizedLearningRate, Sequential, SpectralNormalization
 
 __all__ = ["GeneratorEMA", "clone_structure"]
 
@@ -89,6 +89,11 @@ def _clone_layer(layer):
     # the copy starts from the live layer's CURRENT values: ParamStore copies a variable it finds in `vars` and draws from the
     # weight-initialisation RNG only for one it does not find, and it rebinds the COPY's dict, never the live layer's
     c.vars = dict(layer.vars)
+    if isinstance(layer, (SpectralNormalization, EqualizedLearningRate)):
+        # a wrapper shares ONE dict with the layer it wraps: the copy gets an inner layer of its own, bound to the copy's dict
+        # (a shallow copy alone would leave the clone's inner layer on the live model's variables)
+        c.layer = copy.copy(layer.layer)
+        c.layer.vars = c.vars
     if isinstance(layer, Sequential):
         c.layers = [_clone_layer(l) for l in layer.layers]
         c._store = c._net = c.optimizer = None

@@ -28,7 +28,7 @@ import torch
 
 from . import dist, ops
 from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_LRELU
-from .layers import SpectralNormalization
+from .layers import EqualizedLearningRate, SpectralNormalization
 
 
 RESAMPLE = ("upsample", "avgpool")
@@ -354,7 +354,12 @@ class Net:
         # layers.SpectralNormalization: the engine reads W / sigma (and its transposed copy) of these from the store's effective-weight
         # buffer, which spectral_update() fills; the plain conv layers keep their batched transpose
         self.spectral_layers = [st.lin for st in self.stages if isinstance(st.lin, SpectralNormalization)]
-        self.plain_conv_layers = [l for l in self.conv_layers if not isinstance(l, SpectralNormalization)]
+        # layers.EqualizedLearningRate: c * W (and its transposed copy) likewise, filled by eqlr_update()
+        self.eqlr_layers = [st.lin for st in self.stages if isinstance(st.lin, EqualizedLearningRate)]
+        if self.spectral_layers and self.eqlr_layers:
+            raise NotImplementedError("SpectralNormalization and EqualizedLearningRate layers in one model are not supported: both lay "
+                                      "out the store's effective-weight buffer")
+        self.plain_conv_layers = [l for l in self.conv_layers if not isinstance(l, (SpectralNormalization, EqualizedLearningRate))]
         # power rounds per optimizer step, read ONCE here (0: no wrapped layer): part of the step-program key; changing a layer's
         # power_iterations on a built model has no effect
         rounds = {l.power_iterations for l in self.spectral_layers}
@@ -425,8 +430,10 @@ class Net:
 
     def prepare_weights(self):
         """(Re)builds what the passes read in place of changed weights: W / sigma of the spectrally normalised layers (sigma = v^T W u
-        refreshed, no power round) and the transposed kernel copies the 'other direction' of each conv needs."""
+        refreshed, no power round), c * W of the equalised-learning-rate layers, and the transposed kernel copies the 'other
+        direction' of each conv needs."""
         self.spectral_update(iterate=False)
+        self.eqlr_update()
         self.store.refresh_transposed(self.plain_conv_layers)
 
     # ---- spectral normalisation (DESIGN.md §5 "Spectral normalisation").  Public names, as the LayerNormalization helpers below:
@@ -448,6 +455,20 @@ class Net:
         (g - <g, W-bar> v u^T) / sigma, u and v held constant.  Linear, with u, v, sigma equal on all ranks: after the all-reduce."""
         if self.spectral_layers:
             ops.spectral.grad(self.store.grad, self.store.eff, self.store.state, self.store.spectral_table(self.spectral_layers))
+
+    # ---- equalised learning rate (DESIGN.md §5 "Equalised learning rate").  Public names for the reason above;
+    # tests/test_eqlr_cpu.py records what these enqueue.
+    def eqlr_update(self):
+        """The wrapped layers' effective weights c * W with their transposed copies: one launch for all layers."""
+        if self.eqlr_layers:
+            table = self.store.eqlr_table(self.eqlr_layers)        # lays out store.eff
+            ops.eqlr.scale(self.store.theta, self.store.eff, table)
+
+    def eqlr_scale_gradients(self):
+        """store.grad holds dL/dW_eff of the wrapped layers (the passes ran on W_eff = c * W): in place, dL/dW = c * dL/dW_eff.
+        Linear, with c equal on all ranks: after the all-reduce, in front of the optimizer."""
+        if self.eqlr_layers:
+            ops.eqlr.grad(self.store.grad, self.store.eqlr_table(self.eqlr_layers))
 
     def blur_taps(self, H, W):
         """(device buffer, tap count) of the layer's CURRENT std for H x W images (gaussian_blur.py:21-31,83-88 through

@@ -205,6 +205,8 @@ class SpectralNormalization(Layer):
     sigma = v^T W u alone (DESIGN.md section 5 "Spectral normalisation")."""
 
     def __init__(self, layer, power_iterations=1, **kw):
+        if isinstance(layer, EqualizedLearningRate):
+            raise NotImplementedError("SpectralNormalization around an EqualizedLearningRate: W / sigma cancels the run-time coefficient c")
         if not isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
             raise NotImplementedError(f"SpectralNormalization wraps a Conv2D, a Conv2DTranspose or a Dense, not {type(layer).__name__}")
         if int(power_iterations) < 1:
@@ -245,6 +247,59 @@ class SpectralNormalization(Layer):
         v = _normalize(W @ u)
         self.vars["vector_v"].copy_(torch.from_numpy(v.astype(np.float32)))
         self.vars["sigma"].copy_(torch.from_numpy(np.array([v @ W @ u], dtype=np.float32)))
+
+
+class EqualizedLearningRate(Layer):
+    """The equalised learning rate of ProGAN / StyleGAN (Karras et al. 2018) around a Conv2D, Conv2DTranspose or Dense: the kernel is
+    drawn from N(0, 1) and the network computes with W_eff = c * W, c = gain / sqrt(fan_in) a constant of the layer, so the optimizer
+    sees dL/dW = c * dL/dW_eff and every layer's weights have the same dynamic range.  fan_in = k * k * (input channels): shape[0]
+    of a Dense kernel, k * k * shape[2] of a Conv2D's, k * k * shape[3] of a Conv2DTranspose's ([k, k, Cout, Cin]: ProGAN's
+    ``upscale2d_conv2d`` rule).  The bias starts at zero and is not scaled.  In a Sequential the wrapper stands for the layer it
+    wraps, as SpectralNormalization does: same kind, shapes, fusion and variables, and no state of its own (DESIGN.md section 5
+    "Equalised learning rate").  ``coefficient``: the fp32 value of c as a Python float, known once the input shape is."""
+
+    def __init__(self, layer, gain=math.sqrt(2), **kw):
+        if isinstance(layer, SpectralNormalization):
+            raise NotImplementedError("EqualizedLearningRate around a SpectralNormalization: W / sigma cancels the run-time coefficient c")
+        if not isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
+            raise NotImplementedError(f"EqualizedLearningRate wraps a Conv2D, a Conv2DTranspose or a Dense, not {type(layer).__name__}")
+        if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not (math.isfinite(gain) and gain > 0):
+            raise ValueError(f"EqualizedLearningRate gain={gain!r}: must be a positive finite number")
+        kw.setdefault("input_shape", layer._declared_input_shape)
+        kw.setdefault("name", "equalized_learning_rate_" + layer.name)
+        super().__init__(**kw)
+        self.layer, self.gain = layer, float(gain)
+        self.kind = layer.kind
+        self.fan_in = self.coefficient = None
+        layer.vars = self.vars      # one set of variables, reachable through either object
+
+    def __getattr__(self, name):    # what the wrapper does not have itself (filters, k, stride, units, activation, ...) is the layer's
+        if name == "layer" or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.layer, name)
+
+    def out_shape(self, in_shape):
+        self._set_coefficient(in_shape)
+        return self.layer.out_shape(in_shape)
+
+    @staticmethod
+    def fan_in_of(kind, kernel_shape):
+        """k * k * (input channels) of a kernel variable of a layer of ``kind``."""
+        sh = tuple(int(v) for v in kernel_shape)
+        return sh[0] if kind == "dense" else sh[0] * sh[1] * sh[3 if kind == "convT" else 2]
+
+    def _set_coefficient(self, in_shape):
+        cin = int(in_shape[-1])
+        self.fan_in = cin if self.kind == "dense" else self.layer.k * self.layer.k * cin
+        self.coefficient = float(np.float32(self.gain / math.sqrt(self.fan_in)))      # in double, rounded to fp32 once
+
+    def var_specs(self, in_shape):
+        specs = list(self.layer.var_specs(in_shape))
+        shape = specs[0][1]
+        self._set_coefficient(in_shape)
+        assert self.fan_in == self.fan_in_of(self.kind, shape), (self.fan_in, shape)
+        normal = lambda rng: rng.standard_normal(shape).astype(np.float32)
+        return [("kernel", shape, True, normal)] + specs[1:]         # the bias keeps its zeros
 
 
 class LeakyReLU(Layer):
@@ -410,6 +465,10 @@ class ParamStore:
         self.eff = None
         self._sn = {}           # id(layer) -> (effective kernel view, transposed view or None)
         self._sn_table = None
+        # equalised-learning-rate layers: c * W and its transposed copy in the same buffer, laid out by eqlr_table() (a model has
+        # wrappers of one kind only: engine.Net refuses the mixture)
+        self._eq = {}           # id(layer) -> (effective kernel view, transposed view or None)
+        self._eq_table = None
         for layer in fresh_spectral:
             layer.init_state()
         self.tr_dirty = True
@@ -464,11 +523,17 @@ class ParamStore:
 
     def kernel(self, layer, transposed=False):
         """The kernel the engine computes with: the layer's own variable (``transposed``: its [k*k][C][R] copy), or for a spectrally
-        normalised layer W / sigma and its transposed copy in the effective-weight buffer."""
+        normalised layer W / sigma, for an equalised-learning-rate layer c * W, and its transposed copy in the effective-weight
+        buffer."""
         if isinstance(layer, SpectralNormalization):
             views = self._sn.get(id(layer))
             if views is None:
                 raise KeyError("effective weights are laid out by spectral_table(); call Net.prepare_weights() first")
+            return views[1 if transposed else 0]
+        if isinstance(layer, EqualizedLearningRate):
+            views = self._eq.get(id(layer))
+            if views is None:
+                raise KeyError("effective weights are laid out by eqlr_table(); call Net.prepare_weights() first")
             return views[1 if transposed else 0]
         return self.transposed_kernel(layer) if transposed else layer.vars["kernel"]
 
@@ -500,6 +565,33 @@ class ParamStore:
         self._sn = {k: (self.eff[e:e + n].view(shape), None if t < 0 else self.eff[t:t + n]) for k, (e, t, n, shape) in views.items()}
         table = ops.SpectralTable(ops.spectral.rows(rows), self.device)
         self._sn_table = (key, table)
+        return table
+
+    def eqlr_table(self, layers):
+        """The descriptor table (ops.EqlrTable) of the equalised-learning-rate ``layers`` and, with it, the effective-weight buffer:
+        per layer c * W [K, N] and, for conv kinds, the transposed copy the other direction of the conv reads; 4-float aligned."""
+        key = [id(l) for l in layers]
+        if self._eq_table is not None and self._eq_table[0] == key:
+            return self._eq_table[1]
+        from . import ops
+        pad = lambda n: -(-n // self.ALIGN) * self.ALIGN
+        rows, views, off = [], {}, 0
+        for layer in layers:
+            w = layer.vars["kernel"]
+            K, N, taps = SpectralNormalization.matrix_shape(w.shape)
+            w_off = (w.data_ptr() - self.theta.data_ptr()) // 4
+            assert 0 <= w_off < self.theta.numel() and w_off % 4 == 0
+            eff_off, off = off, off + pad(K * N)
+            tr_off = -1
+            if layer.kind in ("conv", "convT"):
+                tr_off, off = off, off + pad(K * N)
+            rows.append(dict(w_off=w_off, eff_off=eff_off, tr_off=tr_off, K=K, N=N, taps=taps, c=layer.coefficient))
+            views[id(layer)] = (eff_off, tr_off, K * N, tuple(w.shape))
+        self.eff = torch.empty(max(off, 4), dtype=torch.float32, device=self.device)
+        self._eq = {k: (self.eff[e:e + n].view(shape), None if t < 0 else self.eff[t:t + n]) for k, (e, t, n, shape) in views.items()}
+        table = ops.EqlrTable(ops.eqlr.rows(rows), self.device)
+        ops.eqlr.check_table(table.host, self.theta.numel(), self.eff.numel())
+        self._eq_table = (key, table)
         return table
 
     def transposed_kernel(self, layer):
@@ -683,10 +775,18 @@ class Sequential(Layer):
 
 class SpectralSequential(Sequential):
     """A Sequential that, with its ``spectral_norm`` attribute set, wraps every Conv2D, Conv2DTranspose and Dense added to it into a
-    SpectralNormalization (the DCGAN stacks' ``spectral_norm=`` argument)."""
+    SpectralNormalization (the DCGAN stacks' ``spectral_norm=`` argument), or with ``equalized_lr`` set into an
+    EqualizedLearningRate (their ``equalized_lr=`` argument) of gain ``gain``: by default sqrt(2), the gain of a layer in front of a
+    LeakyReLU, and 1 for a layer with a fused tanh."""
     spectral_norm = False
+    equalized_lr = False
 
-    def add(self, layer):
-        if self.spectral_norm and isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
-            layer = SpectralNormalization(layer)
+    def add(self, layer, gain=None):
+        if isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
+            if self.spectral_norm:
+                layer = SpectralNormalization(layer)
+            elif self.equalized_lr:
+                if gain is None:
+                    gain = 1.0 if getattr(layer, "activation", None) == "tanh" else math.sqrt(2)
+                layer = EqualizedLearningRate(layer, gain=gain)
         super().add(layer)

@@ -28,7 +28,12 @@ PixelNormalization in front of the Dense (with either normalisation).  Both comb
 ``spectral_norm=True``.
 
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
-engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``."""
+engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``.
+
+``equalized_lr=True`` (either stack) wraps them into ``layers.EqualizedLearningRate`` instead (ProGAN / StyleGAN's equalised
+learning rate): kernels drawn from N(0, 1), the engine computes with c * W, c = gain / sqrt(fan_in); gain sqrt(2) for every layer in
+front of a LeakyReLU, 1 for the tanh output layer and for the critic's Dense(1).  No new variables.  It combines with every other
+argument but ``spectral_norm=True`` (``ValueError``: W / sigma would cancel c)."""
 from __future__ import annotations
 
 from . import layers
@@ -51,9 +56,11 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 class DCGANGenerator(layers.SpectralSequential):
     def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, normalization="batch",
-                 normalize_latents=False, **kwargs):
+                 normalize_latents=False, equalized_lr=False, **kwargs):
         super().__init__(*args, **kwargs)
-        self.spectral_norm = bool(spectral_norm)
+        self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
+        if self.spectral_norm and self.equalized_lr:
+            raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
         if upsampling not in ("transpose", "resize"):
             raise ValueError(f"upsampling must be 'transpose' or 'resize', got {upsampling!r}")
         if normalization not in ("batch", "pixel"):
@@ -100,9 +107,11 @@ class DCGANGenerator(layers.SpectralSequential):
 
 class DCGANDiscriminator(layers.SpectralSequential):
     def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, spectral_norm=False, minibatch_stddev=None,
-                 **kwargs):
+                 equalized_lr=False, **kwargs):
         super().__init__(*args, **kwargs)
-        self.spectral_norm = bool(spectral_norm)
+        self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
+        if self.spectral_norm and self.equalized_lr:
+            raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
         if downsampling not in ("stride", "pool"):
             raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
         if normalization not in (None, "layer"):
@@ -124,4 +133,4 @@ class DCGANDiscriminator(layers.SpectralSequential):
         if self.minibatch_stddev is not None:
             self.add(layers.MinibatchStdDev(group_size=self.minibatch_stddev))
         self.add(layers.Flatten())
-        self.add(layers.Dense(1, activation="linear"))
+        self.add(layers.Dense(1, activation="linear"), gain=1.0)

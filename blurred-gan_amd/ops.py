@@ -632,6 +632,68 @@ class spectral:
         return grad
 
 
+# ------------------------------------------------------------------ equalised learning rate (include/bgan.h "equalised learning rate")
+class EqlrTable:
+    """The descriptor table of one batch of wrapped layers: the rows in host memory (the calls check them before anything touches
+    the device) and their device copy (the kernels read it)."""
+
+    def __init__(self, rows, device):
+        import numpy as np
+        self.host = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, _lib.EQLR_DESC_INTS)
+        self.n = int(self.host.shape[0])
+        self.dev = torch.from_numpy(self.host.copy()).to(device)
+
+
+class eqlr:
+    """The EqualizedLearningRate kernels, batched over an EqlrTable.  A namespace for the reason ``spectral`` is one."""
+
+    @staticmethod
+    def plan(K, N, taps=1):
+        """How the kernels cut a [K, N] matrix: dict(tiles, vec, grad_units, unit_elems)."""
+        names = ("tiles", "vec", "grad_units", "unit_elems")
+        v = [C.c_int() for _ in names]
+        check(_lib.load().bg_eqlr_plan(int(K), int(N), int(taps), *[C.byref(x) for x in v]), "bg_eqlr_plan")
+        return {k: x.value for k, x in zip(names, v)}
+
+    @staticmethod
+    def rows(layers):
+        """Table rows for ``layers`` = [dict(w_off, eff_off, tr_off, K, N, taps, c)]: the first units are running sums of what ``plan``
+        gives, ``c`` goes in as the bits of its fp32 value."""
+        import numpy as np
+        out, tf, uf = [], 0, 0
+        for l in layers:
+            p = eqlr.plan(l["K"], l["N"], l["taps"])
+            bits = int(np.array([l["c"]], dtype=np.float32).view(np.int32)[0])
+            out.append([l["w_off"], l["eff_off"], l["tr_off"], l["K"], l["N"], l["taps"], tf, uf, bits, 0, 0, 0])
+            tf, uf = tf + p["tiles"], uf + p["grad_units"]
+        return out
+
+    @staticmethod
+    def _host(rows):
+        assert rows.dtype.name == "int32" and rows.flags["C_CONTIGUOUS"] and rows.shape[1] == _lib.EQLR_DESC_INTS
+        return rows.ctypes.data, int(rows.shape[0])
+
+    @staticmethod
+    def check_table(host_rows, theta_floats, eff_floats):
+        """Raises what ``scale`` / ``grad`` would raise for this host table and these buffer sizes; touches no device."""
+        check(_lib.load().bg_eqlr_check_table(*eqlr._host(host_rows), int(theta_floats), int(eff_floats)), "bg_eqlr_check_table")
+
+    @staticmethod
+    def scale(theta, eff, table):
+        """eff = c * W per layer, with the transposed copies of the conv kernels."""
+        _f32(theta, eff)
+        check(_lib.load().bg_eqlr_scale_f32(_ptr(theta), theta.numel(), _ptr(eff), eff.numel(), _ptr(table.dev), *eqlr._host(table.host), _stream()),
+              "bg_eqlr_scale_f32")
+        return eff
+
+    @staticmethod
+    def grad(grad, table):
+        """In place on the flat gradient buffer: dL/dW_eff -> dL/dW = c * dL/dW_eff over each wrapped kernel's segment."""
+        _f32(grad)
+        check(_lib.load().bg_eqlr_grad_f32(_ptr(grad), grad.numel(), _ptr(table.dev), *eqlr._host(table.host), _stream()), "bg_eqlr_grad_f32")
+        return grad
+
+
 # ------------------------------------------------------------------ pointwise / losses / optimisers / rng
 def lerp(r, f, alpha_b, out):
     B = r.shape[0]

@@ -543,6 +543,7 @@ class WGAN:
                 D.gp_second_order(D.context(B, "hat"), self._gp_v0(D, g, norms, aug=aug_hat), reducer=red)
         red.finish()
         D.spectral_project_gradients()
+        D.eqlr_scale_gradients()    # an equalised-learning-rate critic: dL/dW = c * dL/dW_eff
         optimizers.get_optimizer(self.discriminator).apply(store)
         disc_loss = None              # inside train_on_batch the value is read with the rest of the step's metrics
         if self.sync_metrics and not self._defer_metrics:
@@ -643,6 +644,7 @@ class WGAN:
         G.backward(cg, dfakes, need_dx=False, need_dw=True, beta=0.0, scale=1.0, reducer=red)
         red.finish()
         G.spectral_project_gradients()
+        G.eqlr_scale_gradients()
         optimizers.get_optimizer(self.generator).apply(store)
         if self.generator_ema is not None:
             self._update_generator_ema()

@@ -32,9 +32,11 @@ class DCGANGenerator(layers.SpectralSequential):
     """demo_mnist.py:48-71."""
 
     def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, normalization="batch", normalize_latents=False,
-                 **kwargs):
+                 equalized_lr=False, **kwargs):
         super().__init__(*args, **kwargs)
-        self.spectral_norm = bool(spectral_norm)
+        self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
+        if self.spectral_norm and self.equalized_lr:
+            raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
         self.latent_size = latent_size
         resize = {"transpose": False, "resize": True}[upsampling]
         pixel = {"batch": False, "pixel": True}[normalization]
@@ -76,9 +78,12 @@ class DCGANGenerator(layers.SpectralSequential):
 class DCGANDiscriminator(layers.SpectralSequential):
     """demo_mnist.py:74-86."""
 
-    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, minibatch_stddev=0, **kwargs):
+    def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, minibatch_stddev=0, equalized_lr=False,
+                 **kwargs):
         super().__init__(*args, **kwargs)
-        self.spectral_norm = bool(spectral_norm)
+        self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
+        if self.spectral_norm and self.equalized_lr:
+            raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
         pool = {"stride": False, "pool": True}[downsampling]
         norm = {"none": False, "layer": True}[normalization]
         strides = (1, 1) if pool else (2, 2)
@@ -99,7 +104,7 @@ class DCGANDiscriminator(layers.SpectralSequential):
         if minibatch_stddev:
             self.add(layers.MinibatchStdDev(group_size=minibatch_stddev))
         self.add(layers.Flatten())
-        self.add(layers.Dense(1))
+        self.add(layers.Dense(1), gain=1.0)
 
 
 def make_parser():
@@ -136,6 +141,12 @@ def make_parser():
     parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
                         help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
                              "the generator average)")
+    parser.add_argument("--critic-equalized-lr", dest="critic_equalized_lr", action="store_true",
+                        help="equalised learning rate (Karras et al. 2018) on every Conv2D and Dense of the critic: kernels drawn "
+                             "from N(0, 1), the step computes with gain / sqrt(fan_in) * W (not together with its spectral norm)")
+    parser.add_argument("--generator-equalized-lr", dest="generator_equalized_lr", action="store_true",
+                        help="equalised learning rate on every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
+                             "its spectral norm)")
     parser.add_argument("--dataset", default=None, metavar="PATH",
                         help="uint8 .npy of images: train from a device-resident DeviceDataset (default: the data path described above)")
     parser.add_argument("--flip", action="store_true", help="with --dataset: mirror each sample left-right with probability 1/2")
@@ -196,9 +207,9 @@ def main(argv=None):
     config.checkpoint_dir = config.log_dir + "/checkpoints"
 
     gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
-                         normalize_latents=args.normalize_latents)
+                         normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
-                              minibatch_stddev=args.critic_mbstd)
+                              minibatch_stddev=args.critic_mbstd, equalized_lr=args.critic_equalized_lr)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

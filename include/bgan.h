@@ -418,6 +418,33 @@ int bg_spectral_scale_f32(const float* theta, const float* state, float* eff, co
 int bg_spectral_grad_f32(float* grad, const float* eff, const float* state, const int* desc_d, const int* desc_h, int n, float* ws_d,
                          size_t ws_bytes, void* stream);
 
+/* ---- equalised learning rate (Karras et al. 2018; layers.EqualizedLearningRate) ------------------------------------------
+ * A wrapped layer's kernel W[K, N] (as above) is drawn from N(0, 1); the engine runs on W_eff = c * W with the per-layer constant
+ * c = gain / sqrt(fan_in), and the optimizer sees dL/dW = c * dL/dW_eff.
+ *
+ * Both calls are batched over all wrapped layers of one model.  The table has BG_EQLR_DESC_INTS int32 per layer:
+ *   {w_off, eff_off, tr_off, K, N, taps, tile_first, unit_first, c, 0, 0, 0}           (c: the bits of the fp32 coefficient)
+ * w_off: floats from `theta` (and from the flat gradient buffer); eff_off / tr_off: from the effective-weight base (tr_off = -1: no
+ * transposed copy); all multiples of 4.  taps divides K.  tile_first / unit_first: the layer's first work unit in the scale and in
+ * the gradient kernel -- running sums of bg_eqlr_plan's tiles / grad_units.  The table is handed over twice: desc_d on the device,
+ * which the kernels read, and the same rows in host memory, desc_h, which the call checks before anything touches the device: null
+ * pointer BG_ERR_NULL; K / N / taps <= 0, first units that do not continue the table, c not positive and finite, a segment that
+ * ends behind its buffer (`*_floats`: the floats behind each base) or overlaps another BG_ERR_BAD_SHAPE; a base or an offset that
+ * is not 16-byte aligned BG_ERR_BAD_ALIGNMENT.  Every element is written by one thread and multiplied once: the same bits from run
+ * to run and for any batching of the layers. */
+#define BG_EQLR_DESC_INTS 12
+/* pure host query: the 64 x 64 tiles of the scale kernel, its access width (4: R = K / taps and N both multiples of 4, else 1), the
+ * units of the gradient kernel and the floats of one unit */
+int bg_eqlr_plan(int K, int N, int taps, int* tiles, int* vec, int* grad_units, int* unit_elems);
+/* pure host query: the status the two calls below would give this table (eff_floats: of the effective-weight buffer) */
+int bg_eqlr_check_table(const int* desc_h, int n, size_t theta_floats, size_t eff_floats);
+/* eff[eff_off + i] = c * W[i] (one fp32 multiply), and where tr_off >= 0 the copy eff[tr_off + (t * N + col) * R + r] of element
+ * (t * R + r, col), R = K / taps: the [taps][C][R] array bg_conv2d_fwd reads, out of the same launch */
+int bg_eqlr_scale_f32(const float* theta, size_t theta_floats, float* eff, size_t eff_floats, const int* desc_d, const int* desc_h, int n,
+                      void* stream);
+/* g[w_off + i] *= c in place for i < K * N of every layer; nothing else of the buffer is written */
+int bg_eqlr_grad_f32(float* grad, size_t grad_floats, const int* desc_d, const int* desc_h, int n, void* stream);
+
 /* ---- pointwise ------------------------------------------------------------------------------ */
 /* wgan.py:239: xhat[b,:] = r[b,:] + alpha[b] * (f[b,:] - r[b,:]) */
 int bg_lerp_f32(const float* r, const float* f, const float* alpha_b, float* xhat, int B, int n_per, void* stream);
