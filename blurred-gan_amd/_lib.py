@@ -113,6 +113,8 @@ SIGNATURES = {
     "bg_copy_f32": (_i, [_p, _p, _z, _p]),
     "bg_upsample2x_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _f, _f, _p]),
     "bg_pool2x_sum_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _i, _f, _p]),
+    "bg_fir_upsample2x_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _f, _p, _p, _f, _f, _p]),
+    "bg_fir_downsample2x_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _f, _p]),
     "bg_wgangp_d_loss": (_i, [_p, _p, _p, _i, _f, _f, _f, _f, _p, _p, _p, _p]),
     "bg_wgan_g_loss": (_i, [_p, _i, _f, _p, _p, _p]),
     "bg_gan_d_loss": (_i, [_p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p]),

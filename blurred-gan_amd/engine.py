@@ -4,7 +4,9 @@ written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
 A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization] [+ LeakyReLU |
 tanh] [+ Dropout | PixelNormalization]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
-one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose).  MinibatchStdDev is a stage of its
+one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose), and so are their FIR-filtered
+counterparts FilteredUpSampling2D / FilteredDownSampling2D (bg_fir_upsample2x_nhwc_f32 / bg_fir_downsample2x_nhwc_f32 with the taps
+flipped for the transpose).  MinibatchStdDev is a stage of its
 own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent and source).  Stage fusion on the device:
   conv (+bias) + LeakyReLU + Dropout      -> one launch (epilogue of the MFMA kernel)
   dgrad + LeakyReLU'/Dropout' of the stage below -> one launch (BG_EPI_MUL_GRAD epilogue)
@@ -31,7 +33,8 @@ from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_L
 from .layers import EqualizedLearningRate, SpectralNormalization
 
 
-RESAMPLE = ("upsample", "avgpool")
+RESAMPLE = ("upsample", "avgpool", "firup", "firdown")      # "fir*": the FIR-filtered pair (layers.Filtered*Sampling2D)
+UPSAMPLERS = ("upsample", "firup")          # their backward is a down-sampler: nothing to fuse a LeakyReLU' into
 PARAMETER_FREE = RESAMPLE + ("mbstd",)      # stages of their own without variables (layers.MinibatchStdDev: not linear, see mbstd_*)
 SOURCE_KINDS = ("ln", "mbstd")              # _gp_kinds: stages that are not piecewise linear and add a source term to the penalty
 
@@ -681,8 +684,27 @@ class Net:
         """Forward of a resampling stage; linear and parameter-free, so also its linearised forward in the gradient penalty."""
         if st.kind == "upsample":
             ops.upsample2x(x, y, 1.0)
-        else:
+        elif st.kind == "avgpool":
             ops.pool2x_sum(x, y, 0.25)
+        elif st.kind == "firup":            # StyleGAN2's gain: factor ** 2
+            ops.fir_upsample2x(x, y, st.lin.taps, 4.0)
+        else:
+            ops.fir_downsample2x(x, y, st.lin.taps, 1.0)
+
+    @staticmethod
+    def resample_transposed(st, g, tgt, **mul_grad):
+        """Backward of a resampling stage: its transpose on the output gradient ``g``.  ``mul_grad`` (ref / keep / alpha / grad_scale,
+        down-samplers only): LeakyReLU' / Dropout' of the stage below ride in the same launch.  (A public name, as the
+        LayerNormalization helpers below carry: the engine-trace fixture's configurations have no filtered stage;
+        tests/test_firsample_cpu.py records what the two filtered kinds enqueue.)"""
+        if st.kind == "upsample":
+            ops.pool2x_sum(g, tgt, 1.0)
+        elif st.kind == "avgpool":
+            ops.upsample2x(g, tgt, 0.25, **mul_grad)
+        elif st.kind == "firup":            # <UP_f x, g> = <x, DOWN_flip(f) g>
+            ops.fir_downsample2x(g, tgt, st.lin.flipped_taps, 4.0)
+        else:
+            ops.fir_upsample2x(g, tgt, st.lin.flipped_taps, 1.0, **mul_grad)
 
     def predict(self, x, training=False):
         B = x.size(0)
@@ -838,20 +860,18 @@ class Net:
         the data gradient's epilogue or in the pooling backward)."""
         ctx = p.ctx
         if st.kind == "mbstd": return self.mbstd_backward(p, i, st, prev, dz)      # noqa: E701
-        fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense", "upsample")
+        fuse = prev is not None and prev.fusable_grad and st.kind not in ("dense",) + UPSAMPLERS
         # the gradient at an LN (or PixelNormalization) stage's output lands in that stage's dz buffer and is turned into dz in place
         # -- except where a row exceeds what a wave holds in registers (ops.layernorm.route / ops.pixelnorm.route: chunks > 1), where
         # the kernel wants a buffer of its own
         below = ctx.gin if prev is not None and self.rereads_rows(prev) else ctx.dz
         tgt = (ctx.buf(below, i - 1) if i > 0 else ctx.input_grad()).view(ctx.B, *st.in_shape)
-        if st.kind == "upsample":           # transpose of the upsample
-            ops.pool2x_sum(dz.view(ctx.B, *st.out_shape), tgt, 1.0)
-        elif st.kind == "avgpool" and not fuse:
-            ops.upsample2x(dz.view(ctx.B, *st.out_shape), tgt, 0.25)
-        elif st.kind == "avgpool":          # one launch instead of upsample + mul_grad
+        if st.kind in RESAMPLE and not fuse:           # the stage's transpose
+            self.resample_transposed(st, dz.view(ctx.B, *st.out_shape), tgt)
+        elif st.kind in RESAMPLE:           # a down-sampler's: one launch instead of upsample + mul_grad
             dzp, ref = dz.view(ctx.B, *st.out_shape), ctx.a[i - 1]
-            ctx.masked_then_tail(i - 1, lambda rows, keep, scale: ops.upsample2x(dzp[rows], tgt[rows], 0.25, ref=ref[rows], keep=keep,
-                                                                                alpha=prev.alpha, grad_scale=scale))
+            ctx.masked_then_tail(i - 1, lambda rows, keep, scale: self.resample_transposed(st, dzp[rows], tgt[rows], ref=ref[rows], keep=keep,
+                                                                                          alpha=prev.alpha, grad_scale=scale))
         else:
             if i == 0 and dx_rows is not None:        # the image gradient is wanted for samples [lo, hi) only
                 lo, hi = dx_rows
@@ -1057,11 +1077,9 @@ class Net:
             if i == 0:
                 break
             tgt = ctx.v[i - 1].view(ctx.B, *st.in_shape)
-            fuse = prev.fusable_grad and st.kind != "upsample"
-            if st.kind == "upsample":
-                ops.pool2x_sum(lam, tgt, 1.0)
-            elif st.kind == "avgpool":
-                ops.upsample2x(lam, tgt, 0.25, **(dict(ref=ctx.a[i - 1], alpha=prev.alpha) if fuse else {}))
+            fuse = prev.fusable_grad and st.kind not in UPSAMPLERS
+            if st.kind in RESAMPLE:
+                self.resample_transposed(st, lam, tgt, **(dict(ref=ctx.a[i - 1], alpha=prev.alpha) if fuse else {}))
             elif fuse:
                 self._conv(st, lam, tgt, True, EPI_MUL_GRAD, ref=ctx.a[i - 1], alpha=prev.alpha)
             else:
@@ -1101,7 +1119,7 @@ class Net:
         tail = [l for l, _ in flat_layers[idx + 1:]]
         head = (len(tail) == 2 and tail[0].kind == "flatten" and tail[1].kind == "dense" and tail[1].units == 1
                 and getattr(tail[1], "activation", None) is None)
-        below = cur is not None and (cur.kind == "avgpool" or (cur.kind == "conv" and cur.bn is None and cur.act == "lrelu"))
+        below = cur is not None and (cur.kind in ("avgpool", "firdown") or (cur.kind == "conv" and cur.bn is None and cur.act == "lrelu"))
         if not (head and below):
             raise NotImplementedError("MinibatchStdDev is supported directly before the critic's Flatten -> Dense(1) only, behind the last "
                                       "conv stage's LeakyReLU / Dropout / AveragePooling2D (not in a generator, not in front of a conv)")

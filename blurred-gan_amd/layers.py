@@ -366,6 +366,75 @@ class AveragePooling2D(Layer):
         return (s[0] // 2, s[1] // 2, s[2])
 
 
+def resample_taps(resample_kernel):
+    """f = k / sum(k) of an even-length 1-D resampling kernel of at most 8 taps: normalised in double, rounded to fp32 once, as a
+    tuple of Python floats (StyleGAN2's ``_setup_kernel``, per axis)."""
+    try:
+        k = [float(v) for v in resample_kernel]
+    except (TypeError, ValueError):
+        raise ValueError(f"resample_kernel {resample_kernel!r}: a sequence of numbers is needed") from None
+    if not k or not all(math.isfinite(v) for v in k) or not sum(k) > 0.0:
+        raise ValueError(f"resample_kernel {resample_kernel!r}: finite numbers with a positive sum are needed")
+    if len(k) % 2 or len(k) > 8:
+        raise NotImplementedError(f"resample_kernel {resample_kernel!r}: only even lengths up to 8 are supported")
+    total = math.fsum(k)
+    return tuple(float(np.float32(v / total)) for v in k)
+
+
+class _FilteredResampling2D(Layer):
+    """What the two FIR-filtered resampling layers share: the kernel, its fp32 taps and the refusals."""
+
+    def __init__(self, resample_kernel, factor, data_format, **kw):
+        super().__init__(**kw)
+        self.taps = resample_taps(resample_kernel)
+        self.resample_kernel = tuple(float(v) for v in resample_kernel)
+        if _pair(factor) != (2, 2):
+            raise NotImplementedError(f"{type(self).__name__} factor {factor!r}: only a factor of 2 is supported")
+        if not _channels_last(data_format):
+            raise NotImplementedError("only data_format='channels_last' (NHWC) is supported")
+
+    @property
+    def flipped_taps(self):
+        """flip(f): the taps of the adjoint operator (the layer's backward)."""
+        return self.taps[::-1]
+
+    def _map(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"{type(self).__name__} needs an [H, W, C] map, got {tuple(s)}")
+        return s
+
+
+class FilteredUpSampling2D(_FilteredResampling2D):
+    """StyleGAN2's ``upsample_2d``: 2x zero-insertion upsampling through the separable low-pass ``resample_kernel`` (normalised to
+    sum 1 per axis, gain 4), zero padding at the border.  With the default (1, 3, 3, 1) it is half-pixel bilinear interpolation in
+    the interior; (1, 1) is nearest-neighbour ``UpSampling2D``.  No variables."""
+    kind = "firup"
+
+    def __init__(self, resample_kernel=(1, 3, 3, 1), size=2, data_format=None, **kw):
+        super().__init__(resample_kernel, size, data_format, **kw)
+        self.size = (2, 2)
+
+    def out_shape(self, s):
+        s = self._map(s)
+        return (2 * s[0], 2 * s[1], s[2])
+
+
+class FilteredDownSampling2D(_FilteredResampling2D):
+    """StyleGAN2's ``downsample_2d``: the separable low-pass ``resample_kernel`` (normalised to sum 1 per axis), zero padding at the
+    border, then every second sample, on maps of even height and width.  (1, 1) is ``AveragePooling2D``.  No variables."""
+    kind = "firdown"
+
+    def __init__(self, resample_kernel=(1, 3, 3, 1), factor=2, data_format=None, **kw):
+        super().__init__(resample_kernel, factor, data_format, **kw)
+        self.factor = 2
+
+    def out_shape(self, s):
+        s = self._map(s)
+        if s[0] % 2 or s[1] % 2:
+            raise NotImplementedError(f"FilteredDownSampling2D on a map of odd height or width {tuple(s)}")
+        return (s[0] // 2, s[1] // 2, s[2])
+
+
 class MinibatchStdDev(Layer):
     """The minibatch standard deviation layer of ProGAN / StyleGAN / StyleGAN2 (``num_new_features = 1``) at the top of a critic:
     [N, H, W, C] -> [N, H, W, C + 1].  Samples are split into groups of ``group_size`` CONSECUTIVE samples (group g is rows

@@ -11,6 +11,12 @@ every stride-2 transposed convolution by nearest-neighbour UpSampling2D + a stri
 ``downsampling="pool"`` every stride-2 convolution by a stride-1 one whose LeakyReLU / Dropout output is average-pooled.  Such a
 stage convolves at the higher resolution: 4x the multiply-adds of the strided layer it replaces.
 
+``upsampling="filtered"`` / ``downsampling="filtered"`` are the same two stacks with the resampling layer replaced by its FIR-filtered
+counterpart: ``layers.FilteredUpSampling2D`` / ``layers.FilteredDownSampling2D`` with ``resample_kernel`` (default (1, 3, 3, 1):
+StyleGAN2's ``upsample_2d`` / ``downsample_2d``; an even length up to 8, asymmetric kernels allowed).  Map sizes, variables and the
+Dense input are those of ``"resize"`` / ``"pool"``; (1, 1) computes exactly what those compute.  They combine with everything
+``"resize"`` / ``"pool"`` combine with.
+
 The critic takes ``normalization="layer"``: a LayerNormalization over the channels between every Conv2D and its LeakyReLU (the
 WGAN-GP paper's critic; BatchNormalization cannot stand there, the penalty is defined per sample).  Map sizes are unchanged, every
 block gains 2 * C variables; it combines with ``downsampling="pool"``.
@@ -56,16 +62,17 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 class DCGANGenerator(layers.SpectralSequential):
     def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, normalization="batch",
-                 normalize_latents=False, equalized_lr=False, **kwargs):
+                 normalize_latents=False, equalized_lr=False, resample_kernel=(1, 3, 3, 1), **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
-        if upsampling not in ("transpose", "resize"):
-            raise ValueError(f"upsampling must be 'transpose' or 'resize', got {upsampling!r}")
+        if upsampling not in ("transpose", "resize", "filtered"):
+            raise ValueError(f"upsampling must be 'transpose', 'resize' or 'filtered', got {upsampling!r}")
         if normalization not in ("batch", "pixel"):
             raise ValueError(f"normalization must be 'batch' or 'pixel', got {normalization!r}")
         self.upsampling, self.normalization, self.normalize_latents = upsampling, normalization, bool(normalize_latents)
+        self.resample_kernel = tuple(resample_kernel)
         pixel = normalization == "pixel"
         base, ch, convt, last = _G[arch]
         k = KSIZE.get(arch, 5)
@@ -86,8 +93,8 @@ class DCGANGenerator(layers.SpectralSequential):
         assert self.output_shape == (None, base, base, ch)
         hw = base
         for filters, stride, act in convt:
-            if stride == 2 and upsampling == "resize":
-                self.add(layers.UpSampling2D())
+            if stride == 2 and upsampling != "transpose":
+                self.add(layers.UpSampling2D() if upsampling == "resize" else layers.FilteredUpSampling2D(self.resample_kernel))
                 self.add(layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=pixel and act is None, activation=act))
             else:
                 self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=pixel and act is None,
@@ -107,20 +114,20 @@ class DCGANGenerator(layers.SpectralSequential):
 
 class DCGANDiscriminator(layers.SpectralSequential):
     def __init__(self, arch="celeba128", *args, downsampling="stride", normalization=None, spectral_norm=False, minibatch_stddev=None,
-                 equalized_lr=False, **kwargs):
+                 equalized_lr=False, resample_kernel=(1, 3, 3, 1), **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
-        if downsampling not in ("stride", "pool"):
-            raise ValueError(f"downsampling must be 'stride' or 'pool', got {downsampling!r}")
+        if downsampling not in ("stride", "pool", "filtered"):
+            raise ValueError(f"downsampling must be 'stride', 'pool' or 'filtered', got {downsampling!r}")
         if normalization not in (None, "layer"):
             raise ValueError(f"normalization must be None or 'layer', got {normalization!r}")
         if minibatch_stddev is not None and (isinstance(minibatch_stddev, bool) or int(minibatch_stddev) != minibatch_stddev):
             raise ValueError(f"minibatch_stddev must be None or a group size, got {minibatch_stddev!r}")
-        self.downsampling, self.normalization = downsampling, normalization
+        self.downsampling, self.normalization, self.resample_kernel = downsampling, normalization, tuple(resample_kernel)
         self.minibatch_stddev = None if minibatch_stddev is None else int(minibatch_stddev)
-        pool = downsampling == "pool"
+        pool = downsampling != "stride"
         for i, c in enumerate(_D[arch]):
             kw = dict(input_shape=list(IMAGE_SHAPE[arch])) if i == 0 else {}
             self.add(layers.Conv2D(c, KSIZE.get(arch, 5), strides=1 if pool else 2, padding="same", **kw))
@@ -129,7 +136,7 @@ class DCGANDiscriminator(layers.SpectralSequential):
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
             if pool:
-                self.add(layers.AveragePooling2D())
+                self.add(layers.AveragePooling2D() if downsampling == "pool" else layers.FilteredDownSampling2D(self.resample_kernel))
         if self.minibatch_stddev is not None:
             self.add(layers.MinibatchStdDev(group_size=self.minibatch_stddev))
         self.add(layers.Flatten())

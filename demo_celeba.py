@@ -30,13 +30,14 @@ class DCGANGenerator(layers.SpectralSequential):
     """demo_celeba.py:51-93."""
 
     def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, normalization="batch", normalize_latents=False,
-                 equalized_lr=False, **kwargs):
+                 equalized_lr=False, resample_kernel=(1, 3, 3, 1), **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
         self.latent_size = latent_size
-        resize = {"transpose": False, "resize": True}[upsampling]
+        resize = {"transpose": None, "resize": layers.UpSampling2D,
+                  "filtered": lambda: layers.FilteredUpSampling2D(resample_kernel)}[upsampling]
         pixel = {"batch": False, "pixel": True}[normalization]
 
         def block(reshape=None):      # behind a linear layer: the reference's BatchNormalization -> LeakyReLU, or LeakyReLU -> PixelNormalization
@@ -59,7 +60,7 @@ class DCGANGenerator(layers.SpectralSequential):
         hw = 4
         for filters, stride in ((512, 1), (256, 2), (128, 2), (64, 2), (32, 2), (16, 2)):
             if resize and stride == 2:      # resize-convolution: nearest-neighbour upsampling, then a stride-1 convolution
-                self.add(layers.UpSampling2D())
+                self.add(resize())
                 self.add(layers.Conv2D(filters, (5, 5), strides=(1, 1), padding='same', use_bias=pixel))
             else:
                 self.add(layers.Conv2DTranspose(filters, (5, 5), strides=(stride, stride), padding='same', use_bias=pixel))
@@ -74,12 +75,13 @@ class DCGANDiscriminator(layers.SpectralSequential):
     """demo_celeba.py:96-124."""
 
     def __init__(self, *args, downsampling="stride", normalization="none", spectral_norm=False, minibatch_stddev=0, equalized_lr=False,
-                 **kwargs):
+                 resample_kernel=(1, 3, 3, 1), **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
-        pool = {"stride": False, "pool": True}[downsampling]
+        pool = {"stride": None, "pool": layers.AveragePooling2D,
+                "filtered": lambda: layers.FilteredDownSampling2D(resample_kernel)}[downsampling]
         norm = {"none": False, "layer": True}[normalization]
         for i, c in enumerate((16, 32, 64, 128, 256, 512)):
             kw = dict(input_shape=[128, 128, 3]) if i == 0 else {}
@@ -89,7 +91,7 @@ class DCGANDiscriminator(layers.SpectralSequential):
             self.add(layers.LeakyReLU())
             self.add(layers.Dropout(0.3))
             if pool:
-                self.add(layers.AveragePooling2D())
+                self.add(pool())
         if minibatch_stddev:
             self.add(layers.MinibatchStdDev(group_size=minibatch_stddev))
         self.add(layers.Flatten())
@@ -106,12 +108,17 @@ def make_parser():
     parser.add_argument("--results_dir", default="results")
     parser.add_argument("--conv-math", dest="conv_math", default="fp32", choices=["fp32", "bf16x6"],
                         help="conv forward / data-gradient math: fp32 (default) or the opt-in split-bf16 kernels")
-    parser.add_argument("--upsampling", default="transpose", choices=["transpose", "resize"],
-                        help="generator resolution steps: stride-2 Conv2DTranspose (default, the reference's) or nearest-neighbour "
-                             "UpSampling2D + stride-1 Conv2D (4x the multiply-adds of the layers it replaces)")
-    parser.add_argument("--downsampling", default="stride", choices=["stride", "pool"],
-                        help="critic resolution steps: stride-2 Conv2D (default, the reference's) or stride-1 Conv2D + AveragePooling2D "
-                             "(4x the multiply-adds of the layers it replaces)")
+    parser.add_argument("--upsampling", default="transpose", choices=["transpose", "resize", "filtered"],
+                        help="generator resolution steps: stride-2 Conv2DTranspose (default, the reference's), nearest-neighbour "
+                             "UpSampling2D + stride-1 Conv2D (4x the multiply-adds of the layers it replaces), or the same with the "
+                             "FIR-filtered FilteredUpSampling2D (StyleGAN2's upsample_2d, --resample-kernel)")
+    parser.add_argument("--downsampling", default="stride", choices=["stride", "pool", "filtered"],
+                        help="critic resolution steps: stride-2 Conv2D (default, the reference's), stride-1 Conv2D + AveragePooling2D "
+                             "(4x the multiply-adds of the layers it replaces), or the same with the FIR-filtered "
+                             "FilteredDownSampling2D (StyleGAN2's downsample_2d, --resample-kernel)")
+    parser.add_argument("--resample-kernel", dest="resample_kernel", default=(1.0, 3.0, 3.0, 1.0), metavar="K",
+                        type=lambda s: tuple(float(v) for v in s.split(",")),
+                        help="the 1-D kernel of --upsampling filtered / --downsampling filtered: comma-separated, an even count up to 8")
     parser.add_argument("--critic-norm", dest="critic_norm", default="none", choices=["none", "layer"],
                         help="critic normalisation: none (default, the reference's) or a LayerNormalization over the channels between "
                              "every Conv2D and its LeakyReLU (the WGAN-GP paper's critic)")
@@ -189,9 +196,10 @@ def main(argv=None):
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
     gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
-                         normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr)
+                         normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr,
+                         resample_kernel=args.resample_kernel)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
-                              minibatch_stddev=args.critic_mbstd, equalized_lr=args.critic_equalized_lr)
+                              minibatch_stddev=args.critic_mbstd, equalized_lr=args.critic_equalized_lr, resample_kernel=args.resample_kernel)
     generator_ema = None
     if args.g_ema_decay is not None:
         generator_ema = GeneratorEMA(decay=args.g_ema_decay)

@@ -485,6 +485,24 @@ int bg_upsample2x_nhwc_f32(const float* x, float* y, int B, int H, int W, int C,
 /* y[b, i, j, c] = scale * ((x[b,2i,2j,c] + x[b,2i,2j+1,c]) + (x[b,2i+1,2j,c] + x[b,2i+1,2j+1,c])): x[B,2H,2W,C] -> y[B,H,W,C], summed
  * in exactly this order. */
 int bg_pool2x_sum_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, float scale, void* stream);
+/* FIR-filtered 2x resampling (StyleGAN2's upsample_2d / downsample_2d) with a separable kernel of 2T taps, T in 1..4.  Per axis,
+ * for n low-resolution entries,
+ *   UP_t(x)[o]   = sum_i t[o - 2i + T - 1] * x[i],  o in [0, 2n)
+ *   DOWN_t(g)[m] = sum_o t[T + 2m - o] * g[o],      m in [0, n)
+ * where a term whose tap index falls outside [0, 2T) or whose sample falls outside the map is absent (zero padding); the 2-D
+ * operators are the products over H and W, and a call computes y = scale * op(x) in one launch, no intermediate map.
+ * <UP_t x, g> = <x, DOWN_flip(t) g> with flip(t)[j] = t[2T - 1 - j]: FilteredUpSampling2D forward = UP_f at scale 4, backward =
+ * DOWN_flip(f) at scale 4; FilteredDownSampling2D forward (and penalty tangent) = DOWN_f at scale 1, backward = UP_flip(f) at
+ * scale 1.  taps = (0.5, 0.5) gives the nearest pair above.  H, W are the LOW-resolution map's in both calls.  taps is a HOST
+ * pointer to n_taps in {2, 4, 6, 8} floats, copied by value into the kernel's arguments: a step program replays them with no device
+ * table.  Routes, alignment and statuses as for the nearest pair; additionally null taps: BG_ERR_NULL, any other n_taps:
+ * BG_ERR_BAD_SHAPE.  ref / keep / alpha / grad_scale of the upsample: as bg_upsample2x_nhwc_f32's, bit for bit this call without
+ * ref followed by bg_mul_grad_f32.  Neither call takes a step-program binding. */
+int bg_fir_upsample2x_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, const float* taps, int n_taps, float scale,
+                               const float* ref /* may be NULL */, const uint8_t* keep /* may be NULL */, float alpha, float grad_scale,
+                               void* stream);
+int bg_fir_downsample2x_nhwc_f32(const float* x, float* y, int B, int H, int W, int C, const float* taps, int n_taps, float scale,
+                                 void* stream);
 
 /* ---- losses (wgan.py:128-130,155-157,272-285) ----------------------------------------------- */
 /* From scores fs[B], rs[B] and the per-sample norms n[B] of the GP gradient:
