@@ -17,11 +17,11 @@ from .gaussian_blur import GaussianBlur2D, blur_images  # noqa: F401
 from .wgan import WGAN, WGANGP, TrainingConfig, gradient_penalty  # noqa: F401
 from .ema import GeneratorEMA  # noqa: F401
 from .data import DeviceDataset, EpochPlan  # noqa: F401
-from .diffaugment import DiffAugment  # noqa: F401
+from .diffaugment import DiffAugment, AdaptiveAugment  # noqa: F401
 from .objective import Objective  # noqa: F401
 from .blurred_gan import BlurredVariant, BlurredWGANGP, BlurredWGAN  # noqa: F401
 
 __all__ = ["layers", "utils", "dist", "gaussian_blur", "wgan", "blurred_gan", "callbacks", "set_seed", "Sequential",
            "GaussianBlur2D", "blur_images", "optimizers", "WGAN", "WGANGP", "TrainingConfig", "gradient_penalty", "BlurredVariant",
-           "BlurredWGANGP", "BlurredWGAN", "ema", "GeneratorEMA", "data", "DeviceDataset", "EpochPlan", "diffaugment", "DiffAugment",
+           "BlurredWGANGP", "BlurredWGAN", "ema", "GeneratorEMA", "data", "DeviceDataset", "EpochPlan", "diffaugment", "DiffAugment", "AdaptiveAugment",
            "objective", "Objective"]

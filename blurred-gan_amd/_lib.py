@@ -87,6 +87,11 @@ SIGNATURES = {
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
     "bg_diffaug_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "bg_diffaug_adjoint_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "bg_diffaug_gated_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
+    "bg_diffaug_gated_adjoint_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "bg_diffaug_decode_gated": (_i, [C.POINTER(_f), _f, _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
+    "bg_ada_stats_f32": (_i, [_p, _i, _p, _p]),
+    "bg_ada_update_f32": (_i, [_p, _p, _p, _f, _i, _f, _p]),
     "bg_mbstd_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "bg_mbstd_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "bg_mbstd_fwd_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _z, _p]),

@@ -5,7 +5,9 @@ buffer in use), ``n_img``, ``n_batches``, ``blur.std`` and the positions of the 
 dropout), so a resumed run continues the uninterrupted one.  With weight averaging on (``WGAN(generator_ema=...)``) the averaged
 generator's two buffers, its update count and its schedule are saved too (``g_ema_*``); a checkpoint without them restores into
 such a model with the averages reset to the restored live weights (and a warning), one with them into a model without the
-feature, which ignores them.  A checkpoint restores only into a model whose optimizers have the
+feature, which ignores them.  With adaptive augmentation (``WGAN(augment=AdaptiveAugment(...))``) the controller's eight floats and
+its configuration are saved as ``aug_state`` / ``aug_config``; a checkpoint with another ``aug_config`` is refused, one without the
+keys restores into the initial state (and a warning).  A checkpoint restores only into a model whose optimizers have the
 same class and static configuration (``ValueError`` otherwise); one written before optimizers were recorded (``m`` / ``v``
 only) is a default Adam's.
 
@@ -110,6 +112,9 @@ class CheckpointManager:
             d["g_ema_state"] = st.state.cpu().numpy()
             d["g_ema_updates"] = np.int64(g.generator_ema_updates)
             d["g_ema_config"] = np.str_(json.dumps(g.generator_ema_config.get_config()))
+        if getattr(g, "_ada_state", None) is not None:
+            d["aug_state"] = g._ada_state.cpu().numpy()
+            d["aug_config"] = np.str_(json.dumps(g.augment.get_config(), sort_keys=True))
         return d
 
     def save(self, checkpoint_number=None):
@@ -147,6 +152,10 @@ class CheckpointManager:
                 raise ValueError(f"{path}: the {'generator' if tag == 'g' else 'discriminator'} was saved with the equalised-learning-rate "
                                  f"coefficients {saved_eqlr}, the model's wrapped layers have {_eqlr_signature(model)}: the raw kernels of "
                                  "one are not the weights of the other (an empty list is a plain model)")
+        ada = getattr(g, "_ada_state", None) is not None
+        if ada and "aug_config" in d.files and json.loads(str(d["aug_config"])) != g.augment.get_config():
+            raise ValueError(f"{path}: saved with the adaptive augmentation {json.loads(str(d['aug_config']))}, the model's is "
+                             f"{g.augment.get_config()}: the controller's state belongs to its configuration")
         g.n_img.assign(int(d["n_img"]))
         g.n_batches.assign(int(d["n_batches"]))
         if "rng_off" in d.files:
@@ -190,4 +199,14 @@ class CheckpointManager:
                     g._warned_no_ema = True
                     warnings.warn(f"{path} holds no averaged generator: the averages start from the restored live weights, "
                                   "update count 0", RuntimeWarning, stacklevel=2)
+        if ada:
+            if "aug_state" in d.files:
+                g._ada_state.copy_(torch.from_numpy(d["aug_state"]))
+                g._sync_ada_metric_slots()
+            else:
+                g.set_augment_p(g.augment.p)          # the initial state
+                if not getattr(g, "_warned_no_ada", False):          # once per model
+                    g._warned_no_ada = True
+                    warnings.warn(f"{path} holds no adaptive-augmentation state: p starts from the configured {g.augment.p}, the "
+                                  "accumulator empty", RuntimeWarning, stacklevel=2)
         return path

@@ -941,11 +941,18 @@ class Net:
         """ctx.aug_input() = T(x) for the pass's (blurred) input batch ``x``: always a copy, with or without blur."""
         cfg, params = ctx.aug
         assert len(self.in_shape) == 3, "DiffAugment needs an [H, W, C] network input"
+        gate = getattr(cfg, "gate", None)       # diffaugment.GatedAugment: rows of 12 uniforms, p read on the device
+        if gate is not None:
+            assert tuple(params.shape) == (ctx.B, 12), f"gated augmentation params {tuple(params.shape)} for a pass of {ctx.B} samples"
+            return ops.diffaug.fwd_gated(x.view(ctx.B, *self.in_shape), ctx.aug_input(), params, gate, **cfg.kernel_args())
         assert tuple(params.shape) == (ctx.B, 8), f"augmentation params {tuple(params.shape)} for a pass of {ctx.B} samples"
         return ops.diffaug.fwd(x.view(ctx.B, *self.in_shape), ctx.aug_input(), params, **cfg.kernel_args())
 
     def aug_linear(self, cfg, params, v, out):
         """out = L v: the linear part of T for the rows ``params`` belongs to (the penalty's second-order seed)."""
+        gate = getattr(cfg, "gate", None)
+        if gate is not None:
+            return ops.diffaug.fwd_gated(v.view(-1, *self.in_shape), out.view(-1, *self.in_shape), params, gate, **cfg.kernel_args(), linear=True)
         return ops.diffaug.fwd(v.view(-1, *self.in_shape), out.view(-1, *self.in_shape), params, **cfg.kernel_args(), linear=True)
 
     def aug_backward(self, ctx, g, dx_rows):
@@ -956,7 +963,11 @@ class Net:
         cfg, params = ctx.aug
         lo, hi = (0, ctx.B) if dx_rows is None else dx_rows
         g = g.view(hi - lo, *self.in_shape)
-        dx = ops.diffaug.adjoint(g, ctx.a0[lo:hi], params[lo:hi], **cfg.kernel_args())
+        gate = getattr(cfg, "gate", None)
+        if gate is not None:
+            dx = ops.diffaug.adjoint_gated(g, ctx.a0[lo:hi], params[lo:hi], gate, **cfg.kernel_args())
+        else:
+            dx = ops.diffaug.adjoint(g, ctx.a0[lo:hi], params[lo:hi], **cfg.kernel_args())
         return dx if self.blur is None else self.apply_blur(dx, g)
 
     # ------------------------------------------------------------------ GP second order

@@ -499,6 +499,63 @@ class diffaug:
                                                  cutout_ratio, _stream()), "bg_diffaug_adjoint_f32")
         return dx
 
+    # ---- the gated calls of adaptive augmentation: params [n, 12], p one float in device memory, read by the kernel itself
+    @staticmethod
+    def decode_gated(u, p, H, W, ops_mask=7, translation_ratio=0.125, cutout_ratio=0.5):
+        """The library's decode of one row of twelve uniforms at probability ``p``, on the host: decode()'s dict (cy, cx: the box's
+        extent, 0 where the cutout did not fire) plus ``fired`` = ops_mask & the gates that fired."""
+        row = (C.c_float * 12)(*[float(v) for v in u])
+        bsc, geo, fired = (C.c_float * 3)(), (C.c_int * 8)(), C.c_int()
+        check(_lib.load().bg_diffaug_decode_gated(row, float(p), int(H), int(W), int(ops_mask), translation_ratio, cutout_ratio, bsc, geo,
+                                                  C.byref(fired)), "bg_diffaug_decode_gated")
+        return dict(zip(("b", "s", "c", "ty", "tx", "y0", "x0", "cy", "cx", "Sy", "Sx", "fired"), [*bsc, *geo, fired.value]))
+
+    @staticmethod
+    def _check_gated(x, y, params, p):
+        _f32(x, y, params, p)
+        assert x.dim() == 4 and x.shape == y.shape and params.numel() == 12 * x.size(0) and p.numel() >= 1
+        return tuple(int(v) for v in x.shape)
+
+    @staticmethod
+    def fwd_gated(x, y, params, p, ops_mask, translation_ratio, cutout_ratio, linear=False):
+        """y = T(x) per sample with every operation of the policy gated by params[:, 8:11] < p[0]."""
+        n, H, W, Cc = diffaug._check_gated(x, y, params, p)
+        check(_lib.load().bg_diffaug_gated_f32(_ptr(x), _ptr(y), _ptr(params), _ptr(p), n, H, W, Cc, int(ops_mask), translation_ratio,
+                                               cutout_ratio, int(bool(linear)), _stream()), "bg_diffaug_gated_f32")
+        return y
+
+    @staticmethod
+    def adjoint_gated(dy, dx, params, p, ops_mask, translation_ratio, cutout_ratio):
+        """dx = L^T dy per sample, gated likewise."""
+        n, H, W, Cc = diffaug._check_gated(dy, dx, params, p)
+        check(_lib.load().bg_diffaug_gated_adjoint_f32(_ptr(dy), _ptr(dx), _ptr(params), _ptr(p), n, H, W, Cc, int(ops_mask), translation_ratio,
+                                                       cutout_ratio, _stream()), "bg_diffaug_gated_adjoint_f32")
+        return dx
+
+
+# ------------------------------------------------------------------ adaptive augmentation's controller (include/bgan.h)
+class ada:
+    """The two controller kernels of adaptive augmentation.  A namespace for the reason ``layernorm`` is one."""
+    STATS_FLOATS, STATE_FLOATS = 4, 8
+
+    @staticmethod
+    def stats(scores, stats):
+        """stats[4] = {sum of sign(scores), count, 0, 0}; sign(0) = sign(NaN) = 0."""
+        _f32(scores, stats)
+        assert stats.numel() >= ada.STATS_FLOATS
+        check(_lib.load().bg_ada_stats_f32(_ptr(scores), int(scores.numel()), _ptr(stats), _stream()), "bg_ada_stats_f32")
+        return stats
+
+    @staticmethod
+    def update(stats, state, metrics_out, target, interval, inv_speed_images):
+        """One step of the controller on state[8] = {p, acc_sign, acc_count, k, r_last, ...}; ``metrics_out`` (2 floats or None)
+        receives {p, r_last}."""
+        _f32(stats, state, metrics_out)
+        assert stats.numel() >= ada.STATS_FLOATS and state.numel() >= ada.STATE_FLOATS and (metrics_out is None or metrics_out.numel() >= 2)
+        check(_lib.load().bg_ada_update_f32(_ptr(stats), _ptr(state), _ptr(metrics_out), float(target), int(interval), float(inv_speed_images),
+                                            _stream()), "bg_ada_update_f32")
+        return state
+
 
 # ------------------------------------------------------------------ minibatch standard deviation (include/bgan.h)
 class mbstd:

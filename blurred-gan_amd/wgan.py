@@ -112,6 +112,13 @@ class WGAN:
         augment = diffaugment.as_augment(augment)      # ValueError likewise
         ema_schedule = ema_mod.as_schedule(generator_ema)      # ValueError likewise
         objective = objective_mod.as_objective(objective, self.uses_gradient_penalty)      # ValueError likewise
+        adaptive = isinstance(augment, diffaugment.AdaptiveAugment)
+        if adaptive and augment.adaptive and objective.loss == "wasserstein" and \
+                not (self.uses_gradient_penalty and float(getattr(hyperparams, "e_drift", 0.0)) != 0.0):
+            # r_t reads the SIGN of the real scores; the Wasserstein loss is invariant to a shift of all scores and only the drift
+            # term holds them near 0 (diffaugment.AdaptiveAugment)
+            raise ValueError("AdaptiveAugment with a target under loss='wasserstein' needs e_drift != 0: nothing else anchors the "
+                             "sign of the critic's real scores (use a fixed p with target=None, or the hinge / nonsaturating loss)")
         self.hparams = hyperparams
         if dist.world_size() > 1 and int(hyperparams.global_batch_size) != int(hyperparams.batch_size) * dist.world_size():
             import warnings
@@ -192,6 +199,19 @@ class WGAN:
         # the critic's input gradient comes back through L^T.  Configuration, not state; off (None, or an empty policy): no launch
         # and no draw is added.  self.images, generate_samples, the SWD callbacks and gradient_penalty() never see it
         self._augment = augment
+        # adaptive augmentation (diffaugment.AdaptiveAugment): the gated launches read p from ada_state[0], a persistent device
+        # buffer {p, acc_sign, acc_count, k, r_last, 0, 0, 0} that the controller kernels of the critic step update (with a target)
+        # and a checkpoint saves; the engine gets the configuration bound to that address.  Slots 12 / 13 of the step's metric
+        # buffer carry p and the last r_t to the host with the step's one read
+        self._ada_state = None
+        self._aug_bound = augment
+        if adaptive:
+            self._ada_state = torch.zeros(ops.ada.STATE_FLOATS, dtype=torch.float32, device=self.device)
+            self._ada_stats = torch.zeros(ops.ada.STATS_FLOATS, dtype=torch.float32, device=self.device)
+            self._aug_bound = diffaugment.GatedAugment(augment, self._ada_state)
+            self.augment_p_metric = Mean("augment_p")
+            self.augment_rt_metric = Mean("augment_rt")
+            self.set_augment_p(augment.p)
         # the objective (objective.py): None / a loss name / an Objective.  The reference objective runs the reference's loss kernels,
         # launch for launch; any other goes through bg_gan_d_loss / bg_gan_g_loss / bg_gp_seed_target_f32, and with penalty_interval
         # k > 1 only every k-th critic step carries the penalty.  Configuration, not state: the phase is n_batches % k
@@ -217,8 +237,28 @@ class WGAN:
 
     @property
     def augment(self):
-        """The DiffAugment in front of the critic, or None (the constructor's ``augment=``, normalised)."""
+        """The DiffAugment (or AdaptiveAugment) in front of the critic, or None (the constructor's ``augment=``, normalised)."""
         return self._augment
+
+    @property
+    def augment_p(self):
+        """The live probability of an AdaptiveAugment: ONE device read (not on the step path; the ``augment_p`` metric arrives with the
+        step's own read).  None for a model without an AdaptiveAugment."""
+        return None if self._ada_state is None else float(self._ada_state[0].item())
+
+    def set_augment_p(self, value):
+        """Writes the probability and clears the controller's accumulator and step count (r_last stays)."""
+        if self._ada_state is None:
+            raise ValueError("set_augment_p: this model has no AdaptiveAugment (construct it with augment=AdaptiveAugment(...))")
+        if not (isinstance(value, numbers.Real) and not isinstance(value, bool) and 0.0 <= value <= 1.0):
+            raise ValueError(f"set_augment_p: the probability must be a number in [0, 1], got {value!r}")
+        r_last = float(self._ada_state[4].item())
+        self._ada_state.copy_(torch.tensor([float(value), 0.0, 0.0, 0.0, r_last, 0.0, 0.0, 0.0], dtype=torch.float32))
+        self._sync_ada_metric_slots()
+
+    def _sync_ada_metric_slots(self):
+        """Metric slots 12 / 13 <- {p, r_last} of the state: what the controller's launch leaves there, after a write from the host."""
+        self._metrics_dev()[12:14].copy_(self._ada_state[[0, 4]])
 
     @property
     def objective(self):
@@ -241,7 +281,8 @@ class WGAN:
 
     @property
     def metrics(self) -> List[Mean]:
-        return [self.real_scores_metric, self.fake_scores_metric, self.gen_loss_metric, self.disc_loss_metric]
+        base = [self.real_scores_metric, self.fake_scores_metric, self.gen_loss_metric, self.disc_loss_metric]
+        return base if self._ada_state is None else base + [self.augment_p_metric, self.augment_rt_metric]
 
     @property
     def metrics_names(self):
@@ -269,15 +310,21 @@ class WGAN:
 
     def _aug_params(self, name, keys, B):
         """(DiffAugment, params [len(keys) * B, 8]) for one pass of the critic, or None without augmentation: ONE draw from the
-        model's own stream for all row blocks of the pass, or the injected [B, 8] arrays ``keys`` names, stacked in that order."""
+        model's own stream for all row blocks of the pass, or the injected [B, 8] arrays ``keys`` names, stacked in that order.  With
+        an AdaptiveAugment the rows are 12 wide (the three gates) and the configuration comes bound to the model's p."""
         if self._augment is None:
             return None
+        cfg = self._aug_bound
+        w = 8 if self._ada_state is None else cfg.row_floats
         inj = [self._inj(k) for k in keys]
         if any(a is not None for a in inj):
             if any(a is None for a in inj):
                 raise ValueError(f"randomness: of {keys} either all or none are injected")
-            return self._augment, torch.cat([self._as_device(a).view(B, 8) for a in inj], 0).contiguous()
-        return self._augment, self._uniform(name, (len(keys) * B, 8))
+            for k, a in zip(keys, inj):
+                if self._ada_state is not None and tuple(a.shape) != (B, w):
+                    raise ValueError(f"randomness[{k!r}] must be [{B}, {w}] uniforms for {self._augment!r}, got {tuple(a.shape)}")
+            return cfg, torch.cat([self._as_device(a).view(B, w) for a in inj], 0).contiguous()
+        return cfg, self._uniform(name, (len(keys) * B, w))
 
     def _vec_scale(self, B):
         """Q1: the reference adds a [B] drift vector to the scalar loss, and GradientTape sums it, which
@@ -288,7 +335,7 @@ class WGAN:
     def train_on_batch(self, reals, *args, randomness=None, **kwargs):
         """wgan.py:86-114.  ``randomness`` (build-side, for parity tests) injects the step's random inputs:
         dict(z_d, z_g, alpha, mask_fake, mask_real) and, with ``augment``, the [B, 8] uniforms aug_fake, aug_real, aug_hat (D-step)
-        and aug_g (G-step)."""
+        and aug_g (G-step); [B, 12] with an AdaptiveAugment (columns 8..10: the gates of colour, translation, cutout)."""
         self.reset_metrics()
         reals = self._as_device(reals)
         self.batch_size = int(reals.shape[0])
@@ -327,6 +374,7 @@ class WGAN:
             self._record_d_metrics(m[:8])
             if g_ran:
                 self._record_g_metrics(m[8:12])
+            self._record_ada_metrics(m)
         self.log_image_summaries()
         self.n_img.assign_add(self.batch_size)
         self.n_batches.assign_add(1)
@@ -383,6 +431,8 @@ class WGAN:
             key += (("generator_ema", E.theta.data_ptr(), E.state.data_ptr(), self.generator_ema_config.static_config()),)
         if self._augment is not None:
             key += (("augment", self._augment.static_config()),)
+        if self._ada_state is not None:
+            key += (("ada", self._ada_state.data_ptr(), self._ada_stats.data_ptr()),)
         return key
 
     @staticmethod
@@ -421,6 +471,23 @@ class WGAN:
         self.real_scores_metric(m[1])
         self.disc_loss_metric(m[2])
         self._record_gp_metrics(m)
+
+    def _record_ada_metrics(self, m):
+        """Slots 12 / 13 of the step's metric read: p and the last r_t as the critic step's controller launch left them."""
+        if self._ada_state is not None:
+            self.augment_p_metric(m[12])
+            self.augment_rt_metric(m[13])
+
+    def _ada_controller(self, real_scores):
+        """The controller's two launches of a critic step, after the loss launch: the sign statistics of the critic's real scores
+        (the un-penalised forward scores the loss used), summed over the replicas, then the update of p.  Recorded in a step
+        program like any launch; nothing is bound and nothing is read."""
+        cfg = self._augment
+        if self._ada_state is None or not cfg.adaptive:
+            return
+        ops.ada.stats(real_scores, self._ada_stats)
+        dist.all_reduce_sum_async(self._ada_stats).wait()       # one process: no collective
+        ops.ada.update(self._ada_stats, self._ada_state, self._metrics_dev()[12:14], cfg.target, cfg.interval, 1.0 / cfg.speed_images)
 
     def _record_g_metrics(self, m):
         self.fake_scores_metric(m[0])                      # Q6: second update of the same Mean
@@ -517,6 +584,7 @@ class WGAN:
                            dx_rows=(2 * B, 3 * B), defer_conv_dw=one_wgrad, keep_u_rows=(2 * B, 3 * B))
             norms = ops.row_norm(g, self._buf("gp_norms", (B,)))
             self._d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds3[:B], ds3[B:2 * B], met)    # same seeds, full metrics
+            self._ada_controller(rs)
             aug_hat = None if aug is None else (aug[0], aug[1][2 * B:3 * B])
             if one_wgrad:
                 # delta-bar_0 goes into the x-hat rows of the pass's (blurred; with augment: augmented) input buffer, where the
@@ -537,6 +605,7 @@ class WGAN:
                 norms, g = self._gp_first_order(reals, fakes, aug_hat)
             ds2 = self._buf("ds2", (2 * B,))
             self._d_loss(fs, rs, norms, inv_gbs, gp_c, e_d, vs, ds2[:B], ds2[B:], met)
+            self._ada_controller(rs)
             D.backward(cfr, ds2.view(2 * B, 1), need_dx=False, need_dw=True, beta=0.0, scale=1.0,
                        reducer=None if penalty else red)
             if penalty:
@@ -549,6 +618,7 @@ class WGAN:
         if self.sync_metrics and not self._defer_metrics:
             m = self._read_metrics()
             self._record_d_metrics(m[:8])
+            self._record_ada_metrics(m)
             disc_loss = m[2]
         return disc_loss, (fakes, reals)
 

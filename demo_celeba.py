@@ -154,6 +154,7 @@ def make_parser():
     parser.add_argument("--diffaugment", default=None, metavar="POLICY",
                         help="differentiable augmentation of every batch the critic sees: comma-separated names out of "
                              "color, translation, cutout (off by default)")
+    blurred_gan.diffaugment.add_ada_arguments(parser)
     parser.add_argument("--loss", default="wasserstein", choices=["wasserstein", "hinge", "nonsaturating"],
                         help="the pair of critic and generator losses: wasserstein (default, the reference's), hinge or the "
                              "non-saturating logistic loss")
@@ -206,7 +207,7 @@ def main(argv=None):
     elif args.g_ema_halflife_images is not None:
         generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
     gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
-                                    generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=args.diffaugment,
+                                    generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=blurred_gan.diffaugment.augment_from_args(args),
                                     objective=blurred_gan.Objective(args.loss, args.penalty_target, args.penalty_on, args.penalty_interval))
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:

@@ -343,6 +343,38 @@ int bg_diffaug_f32(const float* x, float* y, const float* params, int n, int H, 
 int bg_diffaug_adjoint_f32(const float* dy, float* dx, const float* params, int n, int H, int W, int C, int ops_mask,
                            float translation_ratio, float cutout_ratio, void* stream);
 
+/* ---- adaptive augmentation (ADA, Karras et al. 2020): gated DiffAugment and the controller of its probability ---------------------
+ * The gated calls are the two calls above with a per-sample gate on every operation.  params: [n, 12] uniforms; u0..u7 are decoded
+ * exactly as above, u8 / u9 / u10 are the gates of colour / translation / cutout, u11 is unused.  p: ONE float in DEVICE memory, read
+ * by the kernel when it runs (a replayed step program sees the value the controller left there).  An operation of ops_mask fires for
+ * a sample iff its gate < *p, compared in fp32; one that does not fire takes its neutral value and does no arithmetic for that sample
+ * (colour off: the sample is gathered bit for bit and its mean is never formed; translation off: shift 0; cutout off: an empty box).
+ * *p = 1: the ungated call on params[:, :8], bit for bit (u < 1 always holds).  *p = 0, or a sample none of whose gates fired: a
+ * bit-for-bit copy.  The launch geometry is bg_diffaug_plan's for ops_mask, whatever fires.  Refusals and statuses of the ungated
+ * calls, plus BG_ERR_NULL for a null p and BG_ERR_BAD_ALIGNMENT for a misaligned one.  The ungated calls run the code they ran
+ * before these existed: the gate is a template parameter of the kernel, and their instantiations read neither p nor a gate.
+ * bg_diffaug_decode_gated (host): the decode of one row u[12] at probability p.  *fired_mask = ops_mask & fired bits; bsc and geo as
+ * bg_diffaug_decode with the neutral values of what did not fire (geo[4], geo[5]: the box's extent, 0 where the cutout did not fire).
+ *
+ * Controller.  bg_ada_stats_f32: stats[4] = {sum_i sign(scores[i]), n, 0, 0} with sign(0) = sign(NaN) = 0: a sum of +-1 and 0, exact
+ * in fp32 in any order (0 < n < 2^24).  bg_ada_update_f32: state[8] = {p, acc_sign, acc_count, k, r_last, 0, 0, 0};
+ *   acc_sign += stats[0];  acc_count += stats[1];  k += 1;
+ *   when k == interval:  r = acc_sign / acc_count;  p = clamp(p + sgn(r - target) * acc_count * inv_speed_images, 0, 1), sgn(0) = 0,
+ *                        the product and the sum rounded separately;  r_last = r;  acc_sign = acc_count = k = 0
+ * (StyleGAN2-ADA's adjust = sign(r_t - target) * batch * interval / (ada_kimg * 1000)).  metrics_out, if not NULL, receives {p, r_last}
+ * after the update.  target in (-1, 1), inv_speed_images > 0 (BG_ERR_UNSUPPORTED), interval >= 1 (BG_ERR_BAD_SHAPE).  Under data
+ * parallelism the caller sum-all-reduces stats between the two calls.  One workgroup each, plain stores from one lane, no atomics.
+ * No call takes a step-program binding: everything that changes lives in device memory. */
+int bg_diffaug_gated_f32(const float* x, float* y, const float* params /* [n, 12] */, const float* p /* device, 1 float */, int n, int H,
+                         int W, int C, int ops_mask, float translation_ratio, float cutout_ratio, int linear, void* stream);
+int bg_diffaug_gated_adjoint_f32(const float* dy, float* dx, const float* params /* [n, 12] */, const float* p /* device, 1 float */, int n,
+                                 int H, int W, int C, int ops_mask, float translation_ratio, float cutout_ratio, void* stream);
+int bg_diffaug_decode_gated(const float* u /* 12 */, float p, int H, int W, int ops_mask, float translation_ratio, float cutout_ratio,
+                            float* bsc, int* geo, int* fired_mask);
+int bg_ada_stats_f32(const float* scores, int n, float* stats /* [4] */, void* stream);
+int bg_ada_update_f32(const float* stats, float* state /* [8] */, float* metrics_out /* 2 floats, may be NULL */, float target, int interval,
+                      float inv_speed_images, void* stream);
+
 /* ---- minibatch standard deviation (Karras et al. 2018; StyleGAN2's layer with one new feature; layers.MinibatchStdDev) ---------
  * x: [N, P, C] fp32, P pixels; a group is G CONSECUTIVE samples (N % G == 0, G >= 2: BG_ERR_BAD_SHAPE otherwise).  Per group g and
  * column (p, c), with k = 1 / (G * P * C):
