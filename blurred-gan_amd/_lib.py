@@ -82,6 +82,10 @@ SIGNATURES = {
     "bg_pixelnorm_route": (_i, [_i, C.POINTER(_i)]),
     "bg_pixelnorm_fwd_f32": (_i, [_p, _p, _p, _i, _i, _f, _f, _p]),
     "bg_pixelnorm_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
+    "bg_noise_route": (_i, [_i, C.POINTER(_i)]),
+    "bg_noise_add_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
+    "bg_noise_grad_workspace_bytes": (_z, [_i, _i]),
+    "bg_noise_grad_f32": (_i, [_p, _p, _p, _i, _i, _p, _f, _f, _p]),
     "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "bg_diffaug_plan": (_i, [_i, _i, _i, _i, _i] + [C.POINTER(_i)] * 5),
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
@@ -143,6 +147,7 @@ SIGNATURES = {
     "bg_ema_f32": (_i, [_p, _p, _z, _p, _p, _z, _f, _p]),
     "bg_uniform_f32": (_i, [_p, _z, _u64, _u64, _p]),
     "bg_keep_mask_u8": (_i, [_p, _z, _f, _u64, _u64, _p]),
+    "bg_normal_f32": (_i, [_p, _z, _u64, _u64, _p]),
     "bg_program_create": (_i, [C.POINTER(_p), _i]),
     "bg_program_destroy": (_i, [_p]),
     "bg_program_record_begin": (_i, [_p]),
@@ -166,6 +171,7 @@ SIGNATURES = {
 
 COMM_ID_BYTES = 128
 PIXELNORM_ROUTE_INTS = 8       # include/bgan.h BG_PIXELNORM_ROUTE_INTS
+NOISE_ROUTE_INTS = 8           # include/bgan.h BG_NOISE_ROUTE_INTS
 MBSTD_PLAN_INTS = 12          # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 EQLR_DESC_INTS = 12            # include/bgan.h BG_EQLR_DESC_INTS

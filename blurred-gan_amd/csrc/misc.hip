@@ -941,6 +941,40 @@ __global__ __launch_bounds__(kT) void keep_mask_kernel(uint8_t* out, size_t n, f
   }
 }
 
+// N(0, 1) draws by Box-Muller inside a Philox block (third counter word 2): words (0, 1) give elements (0, 1), words (2, 3) give
+// elements (2, 3).  u1 = ((w_a >> 8) + 1) * 2^-24 in (0, 1], u2 = (w_b >> 8) * 2^-24 in [0, 1), r = sqrt(-2 log u1), and the pair is
+// r * cospi(2 u2), r * sinpi(2 u2): |z| <= sqrt(48 log 2) = 5.77, and u1 = 1 gives an exact 0.  The accurate library functions, not
+// the fast intrinsics.
+__device__ inline void box_muller(uint32_t wa, uint32_t wb, float& z0, float& z1) {
+  const float u1 = (float)((wa >> 8) + 1u) * (1.0f / 16777216.0f);
+  const float a = 2.0f * u01(wb);
+  const float r = sqrtf(-2.0f * logf(u1));
+  z0 = r * cospif(a);
+  z1 = r * sinpif(a);
+}
+
+// element e is value e % 4 of the block with counter offset + e / 4; a thread forms one block and leaves it with ONE 16-byte
+// store where the output is 16-byte aligned and the block is whole
+__global__ __launch_bounds__(kT) void normal_kernel(float* out, size_t n, uint64_t seed, uint64_t offset) {
+  const size_t nq = (n + 3) / 4;
+  const bool al16 = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  for (size_t q = (size_t)blockIdx.x * kT + threadIdx.x; q < nq; q += (size_t)gridDim.x * kT) {
+    const uint64_t ctr = offset + q;
+    uint32_t r[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    float z[4];
+    box_muller(r[0], r[1], z[0], z[1]);
+    box_muller(r[2], r[3], z[2], z[3]);
+    if (al16 && q * 4 + 3 < n) {
+      *reinterpret_cast<float4*>(out + q * 4) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (q * 4 + i < n) out[q * 4 + i] = z[i];
+    }
+  }
+}
+
 }  // namespace
 
 #define BG_POINTWISE_PROLOGUE(fn, cond, n_)                                     \
@@ -1398,6 +1432,16 @@ int bg_uniform_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* s
   bg::launch(uniform_kernel, dim3(grid_for(n, 4)), dim3(kT), 0, L.s, out, n, seed, offset);
   bg::bind_last(3, bg::BIND_U64, slot);
   return L.done("uniform_kernel");
+}
+
+int bg_normal_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream) {
+  BG_POINTWISE_PROLOGUE("bg_normal_f32", out, n);
+  BG_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3u) == 0, BG_ERR_BAD_ALIGNMENT, "bg_normal_f32: out must be 4-byte aligned");
+  bg::Launch L(stream, "rng_normal", 0, 4.0 * n);
+  const int slot = bg::take_bind(BG_BIND_RNG_OFFSET);     // step program: the counter offset advances per replay
+  bg::launch(normal_kernel, dim3(grid_for(n, 4)), dim3(kT), 0, L.s, out, n, seed, offset);
+  bg::bind_last(3, bg::BIND_U64, slot);
+  return L.done("normal_kernel");
 }
 
 int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint64_t offset, void* stream) {

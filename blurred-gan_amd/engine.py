@@ -2,8 +2,8 @@
 gradient-penalty linearised forward on the HIP kernels.  There is no tape: every backward formula is
 written out (SURVEY.md 8a, rows T1-T8 and the GP second-order derivation).
 
-A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization] [+ LeakyReLU |
-tanh] [+ Dropout | PixelNormalization]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
+A stage = one linear op (Dense | Conv2D | Conv2DTranspose) [+ bias] [+ BatchNormalization | LayerNormalization | NoiseInjection]
+[+ LeakyReLU | tanh] [+ Dropout | PixelNormalization]; Reshape / Flatten are views.  UpSampling2D / AveragePooling2D are stages of their own: linear, parameter-free,
 one launch each way (bg_upsample2x_nhwc_f32 / bg_pool2x_sum_nhwc_f32, each the other's transpose), and so are their FIR-filtered
 counterparts FilteredUpSampling2D / FilteredDownSampling2D (bg_fir_upsample2x_nhwc_f32 / bg_fir_downsample2x_nhwc_f32 with the taps
 flipped for the transpose).  MinibatchStdDev is a stage of its
@@ -15,6 +15,8 @@ own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent
   LayerNormalization + LeakyReLU + Dropout -> one pass over the conv's stored output (per-pixel statistics, csrc/layernorm.hip)
   LeakyReLU + PixelNormalization          -> one pass over the linear op's stored output (csrc/pixelnorm.hip); a PixelNormalization
                                              that is the network's first layer normalises the latents, one launch, no backward
+  NoiseInjection + LeakyReLU              -> one in-place pass over the conv's stored output (csrc/noise.hip), in front of the
+                                             PixelNormalization pass where the stage has one; all noise maps of a pass are one draw
 
 Net.forward and Net.backward are input / pass set-up, a loop over the stages, and one helper per concern (DESIGN.md §5
 "Engine map"); tests/test_engine_trace_cpu.py holds the order and the arguments of everything they enqueue.
@@ -49,6 +51,7 @@ class Stage:
         self.ln = None              # layers.LayerNormalization between a Conv2D and its LeakyReLU (the critic's normalisation)
         self.pn = None              # layers.PixelNormalization directly behind the stage's LeakyReLU (the generator's normalisation)
         self.pn_channels = None     # the C it normalises over: the last axis of the map at the layer (a Dense's, behind its Reshape)
+        self.noise = None           # layers.NoiseInjection directly behind the stage's Conv2D / Conv2DTranspose (the generator's noise input)
         self.act = getattr(lin, "activation", None)
         self.alpha = 1.0
         self.drop = None
@@ -80,6 +83,11 @@ class Stage:
     @property
     def ln_pixels(self):
         """Rows of an LN stage's [R, C] view per sample: its map's pixels."""
+        return int(np.prod(self.out_shape[:-1]))
+
+    @property
+    def noise_pixels(self):
+        """Noise values of a NoiseInjection stage per sample: its map's pixels."""
         return int(np.prod(self.out_shape[:-1]))
 
     @property
@@ -143,6 +151,18 @@ class Context(_StageBuffers):
                 self.keep[i] = self.keep_flat[offs[i]:offs[i] + n].view((DR,) + st.out_shape)
         rates = {float(st.drop) for st in net.stages if st.drop}
         self.keep_rate = rates.pop() if len(rates) == 1 else None      # None: stages differ, draw per stage
+        # the noise maps of all NoiseInjection stages live in ONE fp32 buffer of B * P floats, P = the stages' pixels per sample:
+        # a pass draws them with one launch.  Stage by stage ([stage][B][H * W]: the kernels read a stage's map as one contiguous
+        # [R] vector); maps handed in are [B, P], per sample in network order, and are dealt out by Net.noise_load
+        self.noise = [None] * len(net.stages)
+        self.noise_flat, self.noise_active = None, False
+        if net.has_noise:
+            P = sum(st.noise_pixels for st in net.stages if st.noise is not None)
+            self.noise_flat, o = f(B * P), 0
+            for i, st in enumerate(net.stages):
+                if st.noise is not None:
+                    self.noise[i] = self.noise_flat[o:o + B * st.noise_pixels]
+                    o += B * st.noise_pixels
         self._net, self._device = net, device
         net.check_rows(B)
         self._extra = {}
@@ -313,6 +333,10 @@ class Net:
                 self.pn_place(flat_layers, idx, cur)
             elif k in ("bn", "layernorm", "dropout", "lrelu") and cur is not None and cur.pn is not None:
                 raise NotImplementedError(self.PN_RULE + f" (a {type(l).__name__} follows the PixelNormalization of its stage)")
+            elif k == "noise":
+                self.noise_place(flat_layers, idx, cur)
+            elif k in ("bn", "layernorm", "dropout") and cur is not None and cur.noise is not None:
+                raise NotImplementedError(self.NOISE_RULE + f" (a {type(l).__name__} in the stage of a NoiseInjection)")
             elif k == "bn":
                 if cur is not None and cur.ln is not None:
                     raise NotImplementedError("LayerNormalization together with BatchNormalization in one stage is not supported")
@@ -350,6 +374,8 @@ class Net:
                 raise NotImplementedError("tanh after BatchNormalization is not on the reference path")
             if st.ln is not None and st.act != "lrelu":
                 raise NotImplementedError("LayerNormalization must be followed by a LeakyReLU")
+            if st.noise is not None and st.act != "lrelu":
+                raise NotImplementedError(self.NOISE_RULE + " (the stage has no LeakyReLU)")
         if self.stages and (self.stages[0].kind in RESAMPLE or self.stages[-1].kind in RESAMPLE):
             raise NotImplementedError("UpSampling2D / AveragePooling2D must stand between two linear layers, not first or last in a network")
         self.out_shape = self.stages[-1].out_shape
@@ -375,6 +401,8 @@ class Net:
         # second-order route, and its first-order backward keeps what the source needs
         self.has_source = self.has_ln or bool(self.mbstd_layers)
         self.has_pn = self.latent_pn is not None or any(st.pn is not None for st in self.stages)
+        self.has_noise = any(st.noise is not None for st in self.stages)
+        self.noise_pixels = sum(st.noise_pixels for st in self.stages if st.noise is not None)     # P: noise values per sample
         self._ctx = {}
         self._rows_checked = set()
         self._ws = None
@@ -525,14 +553,17 @@ class Net:
             return ops.blur_nhwc(x, y, taps, nt, tmp)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, ctx: Context, inputs, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None, augment=None):
+    def forward(self, ctx: Context, inputs, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None, augment=None, noise=None):
         """inputs: a tensor [B,...] or a list of tensors concatenated along the batch.  ``training`` switches
         Dropout and BatchNormalization exactly as Keras' ``training=`` argument does.
         ``lerp_alpha`` (with inputs = [f, r]): a third batch slice x-hat = r + alpha (f - r) follows the two (wgan.py:239).  Behind
         a blur layer of a geometry the row-block kernel takes, all three slices are blurred by ONE launch that forms x-hat on the
         fly (bg_blur3_lerp_nhwc_f32); otherwise x-hat is written to ``lerp_out`` by bg_lerp_f32 and joins the list.
         ``augment`` = (DiffAugment, params [B, 8]): the assembled (blurred) batch goes through T into a second input-sized buffer,
-        which is what stage 0 reads; the pass's backward applies L^T ahead of blur^T (aug_forward / aug_backward)."""
+        which is what stage 0 reads; the pass's backward applies L^T ahead of blur^T (aug_forward / aug_backward).
+        ``noise`` (a network with NoiseInjection stages; in training and in inference alike): None draws the maps of all stages
+        with ONE launch from ``seed`` and this network's counter, as the one-draw keep mask is drawn; a tensor [B, P] (per sample,
+        the stages' maps in network order) is copied in; False leaves the noise launches out, as if every strength were 0."""
         if self.store.tr_dirty:
             self.prepare_weights()
         x = self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)
@@ -544,6 +575,7 @@ class Net:
         one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
         if one_draw:
             ops.keep_mask(ctx.keep_flat[:ctx.keep_total], 1.0 - ctx.keep_rate, seed, counter=(self, "rng_offset"))
+        if self.has_noise: self.noise_draw(ctx, noise, seed)      # noqa: E701
         folded = () if training else self._fold_inference_bns(ctx)
         for i, st in enumerate(self.stages):
             xin = ctx.xin[i] = x.view(ctx.B, *st.in_shape)
@@ -609,6 +641,7 @@ class Net:
         BatchNorm + LeakyReLU pass where it has one of its own."""
         if st.ln is not None: return self.ln_forward(ctx, i, st, xin, out)      # noqa: E701
         if st.pn is not None: return self.pn_forward(ctx, i, st, xin, out)      # noqa: E701
+        if st.noise is not None and ctx.noise_active: return self.noise_forward(ctx, i, st, xin, out)      # noqa: E701
         bias = st.lin.vars.get("bias")
         tgt = ctx.z[i] if st.bn is not None else out
         stat_rows = 0          # rows of BatchNorm statistics partials the conv left behind (0: none)
@@ -832,6 +865,7 @@ class Net:
         B, WB, lin = p.ctx.B, p.dw_rows, st.lin
         xin = p.ctx.xin[i]
         xw, dzw = (xin, dz) if WB == B else (xin[:WB], dz.view(B, *st.out_shape)[:WB])
+        if st.noise is not None: self.noise_backward(p, i, st, dzw)      # noqa: E701
         deferred = p.defer_conv_dw and st.kind == "conv"        # left to gp_second_order_merged, the reducer's hand-over too
         if st.kind == "dense":
             ops.gemm(xw, dzw, self.store.grad_of(lin, "kernel"), st.in_shape[0], st.out_shape[0], WB, transA=True, beta=p.beta, scale=p.scale)
@@ -851,8 +885,9 @@ class Net:
                 p.reducer.ready(*self._train_range(st))
 
     def _train_range(self, st):
-        """The slice of the flat trainable buffer that holds stage ``st``'s variables: its linear op's and its normalisation's."""
-        return self.store.train_range(st.lin, st.bn if st.ln is None else st.ln)
+        """The slice of the flat trainable buffer that holds stage ``st``'s variables: its linear op's, its normalisation's and its
+        noise strength (which lies between the linear op's variables and the next stage's)."""
+        return self.store.train_range(st.lin, st.bn if st.ln is None else st.ln, st.noise)
 
     def _input_grad(self, p, i, st, prev, dz, dx_rows):
         """The gradient w.r.t. stage i's input into the dz buffer of the stage below (the pass's input-gradient buffer at i = 0).
@@ -927,6 +962,7 @@ class Net:
             ops.gemm(xin, self.store.kernel(st.lin), z, ctx.B, st.out_shape[0], st.in_shape[0], bias=bias)
         else:
             self._conv(st, xin, z, False, EPI_NONE, bias=bias)
+        if st.noise is not None and ctx.noise_active: self.noise_add(ctx, i, st, z, 1.0)      # noqa: E701
         ops.pixelnorm.fwd(z, out, ctx.B * st.pn_rows, st.pn_channels, r=ctx.inv[i], eps=st.pn.epsilon, lrelu_alpha=st.alpha)
 
     def pn_backward(self, p, i, st, gv):
@@ -934,6 +970,61 @@ class Net:
         gradient already stands in the stage's dz buffer (_input_grad put it there)."""
         ctx = p.ctx
         return ops.pixelnorm.bwd(gv, ctx.a[i], ctx.inv[i], ctx.buf(ctx.dz, i), ctx.B * st.pn_rows, st.pn_channels, lrelu_alpha=st.alpha)
+
+    # ---- NoiseInjection (DESIGN.md §5 "Noise inputs").  Public names for the reason the LayerNormalization helpers carry them: no
+    # configuration of the engine-trace fixture has the layer; tests/test_noise_cpu.py records what these enqueue.
+    NOISE_RULE = ("NoiseInjection is supported directly behind a Conv2D or Conv2DTranspose (not a Dense or a resampling layer), once per "
+                  "stage, in front of the stage's LeakyReLU, in a stage without BatchNormalization, LayerNormalization, Dropout or tanh")
+
+    def noise_place(self, flat_layers, idx, cur):
+        """Net.__init__'s placement rule for the NoiseInjection at ``flat_layers[idx]``: the noise input of stage ``cur``, whose
+        linear layer stands directly in front of it; everything else is refused."""
+        l, _ = flat_layers[idx]
+        ok = (cur is not None and cur.kind in ("conv", "convT") and idx > 0 and flat_layers[idx - 1][0] is cur.lin and cur.act is None
+              and cur.bn is None and cur.ln is None and not cur.drop and cur.pn is None and cur.noise is None)
+        if not ok:
+            raise NotImplementedError(self.NOISE_RULE)
+        cur.noise = l
+
+    def noise_draw(self, ctx, noise, seed):
+        """The pass's noise maps: drawn (None: one launch for all stages), handed in (a tensor [B, P]) or left out (False)."""
+        ctx.noise_active = noise is not False
+        if noise is None:
+            ops.rng.normal(ctx.noise_flat, seed, counter=(self, "rng_offset"))
+        elif noise is not False:
+            self.noise_load(ctx, noise)
+
+    def noise_load(self, ctx, noise):
+        """Deals maps handed in as [B, P] (per sample, the stages' maps in network order) out to the stages' slices."""
+        P = self.noise_pixels
+        if tuple(noise.shape) != (ctx.B, P):
+            raise ValueError(f"noise must be [{ctx.B}, {P}] (one value per pixel of the {sum(st.noise is not None for st in self.stages)} "
+                             f"NoiseInjection maps, per sample, in network order), got {tuple(noise.shape)}")
+        noise, o = noise.to(self.device, torch.float32), 0
+        for i, st in enumerate(self.stages):
+            if st.noise is not None:
+                n = st.noise_pixels
+                ctx.noise[i].view(ctx.B, n).copy_(noise[:, o:o + n])
+                o += n
+
+    def noise_add(self, ctx, i, st, z, alpha):
+        """z = LeakyReLU_alpha(z + strength * noise) of stage i, in place."""
+        return ops.noise.add(z, ctx.noise[i], st.noise.vars["noise_strength"], z, ctx.B * st.noise_pixels, st.out_shape[-1], lrelu_alpha=alpha)
+
+    def noise_forward(self, ctx, i, st, xin, out):
+        """A NoiseInjection stage without PixelNormalization: the conv (+ bias) into the stage's output, then the noise and the
+        LeakyReLU in place on it."""
+        self._conv(st, xin, out, False, EPI_NONE, bias=st.lin.vars.get("bias"))
+        self.noise_add(ctx, i, st, out, st.alpha)
+
+    def noise_backward(self, p, i, st, dzw):
+        """The strength's gradient of stage i from ``dzw``, the gradient at the conv's output of the pass's first dw_rows samples (the
+        add passes it on unchanged): one launch sequence with the pass's beta / scale.  A pass without noise leaves beta * old."""
+        g = self.store.grad_of(st.noise, "noise_strength")
+        if not p.ctx.noise_active:          # beta * old: nothing to launch where the pass accumulates (beta = 1)
+            return g if p.beta == 1.0 else ops.fill(g, 0.0) if p.beta == 0.0 else ops.scale_(g, p.beta)
+        R, Cc = p.dw_rows * st.noise_pixels, st.out_shape[-1]
+        return ops.noise.grad(dzw, p.ctx.noise[i][:R], g, R, Cc, self.workspace(ops.noise.workspace_bytes(R, Cc)), beta=p.beta, scale=p.scale)
 
     # ---- DiffAugment in front of stage 0 (DESIGN.md §5 "Augmentation").  Public names for the reason the LayerNormalization helpers
     # carry them: the engine-trace fixture's configurations run without augmentation; tests/test_diffaug_cpu.py records these.
@@ -1018,6 +1109,7 @@ class Net:
         Not with LayerNormalization stages: their source backward (gp_ln_source_backward) needs the x-hat rows of the activations
         this pass overwrites, so such a critic takes ``gp_second_order`` on ``ctx.rows(lo, hi)``."""
         if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
+        if self.has_noise: raise NotImplementedError("NoiseInjection in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()
         if set(kinds) & set(SOURCE_KINDS): raise NotImplementedError("gp_second_order_merged overwrites activations the LayerNormalization / MinibatchStdDev source backward needs")  # noqa: E701
         self.store.ensure_opt_state()
@@ -1037,6 +1129,7 @@ class Net:
         dependence on the stage's PRIMAL input adds goes down the network once more in gp_ln_source_backward.  That pass writes the
         last contribution to every layer up to the top-most such stage, so those layers' slices go to the reducer from there."""
         if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
+        if self.has_noise: raise NotImplementedError("NoiseInjection in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()
         self.store.ensure_opt_state()
         top = max((i for i, k in enumerate(kinds) if k in SOURCE_KINDS), default=-1)

@@ -191,6 +191,25 @@ class PixelNormalization(Layer):
         return tuple(s)
 
 
+class NoiseInjection(Layer):
+    """The per-pixel noise input of a StyleGAN synthesis layer (Karras et al. 2019, 2020): ``strength * N(0, 1)`` is added to every
+    pixel of an [H, W, C] map, one draw per pixel broadcast over the channels, with ONE learned scalar ``noise_strength`` that
+    starts at zero (StyleGAN2's; StyleGAN1's per-channel strengths are not built).  It stands directly behind a Conv2D or
+    Conv2DTranspose (its bias included), in front of the stage's LeakyReLU, in the generator only.  The same in training and in
+    inference: every forward draws fresh noise unless it is handed maps or told to leave the noise out
+    (``engine.Net.forward(noise=...)``)."""
+    kind = "noise"
+
+    def out_shape(self, s):
+        if len(s) != 3:
+            raise NotImplementedError(f"NoiseInjection needs an [H, W, C] map, got {tuple(s)}")
+        return tuple(s)
+
+    def var_specs(self, s):
+        self.out_shape(s)
+        return [("noise_strength", (1,), True, _zeros((1,)))]
+
+
 def _normalize(x):
     """x / max(||x||, 1e-12): the normalisation of the power iteration."""
     return x / max(float(np.linalg.norm(x)), 1e-12)

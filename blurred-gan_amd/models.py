@@ -33,6 +33,11 @@ normalisation runs over the channels of the reshaped map.  The tanh output layer
 PixelNormalization in front of the Dense (with either normalisation).  Both combine with ``upsampling="resize"`` and
 ``spectral_norm=True``.
 
+``noise=True`` (the generator, with ``normalization="pixel"`` only; default False: the stack variable for variable as before) puts a
+``layers.NoiseInjection`` behind every (transposed) convolution of the stack except the tanh output layer, in front of its LeakyReLU:
+StyleGAN's per-pixel noise inputs, one learned scalar ``noise_strength`` per layer, initialised to zero.  It combines with everything
+``normalization="pixel"`` combines with.
+
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
 engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``.
 
@@ -62,11 +67,14 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 class DCGANGenerator(layers.SpectralSequential):
     def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, normalization="batch",
-                 normalize_latents=False, equalized_lr=False, resample_kernel=(1, 3, 3, 1), **kwargs):
+                 normalize_latents=False, equalized_lr=False, resample_kernel=(1, 3, 3, 1), noise=False, **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
+        if noise and normalization != "pixel":
+            raise ValueError("noise=True needs normalization='pixel': a NoiseInjection cannot stand in a BatchNormalization stage")
+        self.noise = bool(noise)
         if upsampling not in ("transpose", "resize", "filtered"):
             raise ValueError(f"upsampling must be 'transpose', 'resize' or 'filtered', got {upsampling!r}")
         if normalization not in ("batch", "pixel"):
@@ -101,6 +109,8 @@ class DCGANGenerator(layers.SpectralSequential):
                                                 activation=act))
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
+            if act is None and self.noise:
+                self.add(layers.NoiseInjection())
             if act is None and pixel:
                 self.add(layers.LeakyReLU())
                 self.add(layers.PixelNormalization())

@@ -449,6 +449,41 @@ class pixelnorm:
         return dz
 
 
+# ------------------------------------------------------------------ noise inputs (include/bgan.h "noise inputs")
+class noise:
+    """The NoiseInjection kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's
+    public functions by name; these calls are recorded by the noise tests' own recorder."""
+
+    @staticmethod
+    def route(Cc, aligned=True):
+        """How the kernels lay a row of ``Cc`` channels over a wave: ``pixelnorm.route``'s dict, for these kernels."""
+        v = (C.c_int * _lib.NOISE_ROUTE_INTS)()
+        check(_lib.load().bg_noise_route(int(Cc), v), "bg_noise_route")
+        vec, lanes, regs, chunks = v[0:4] if aligned else v[4:8]
+        return dict(vec=vec, lanes=lanes, regs=regs, chunks=chunks, rows_per_workgroup=4 * (64 // lanes))
+
+    @staticmethod
+    def workspace_bytes(R, Cc):
+        return int(_lib.load().bg_noise_grad_workspace_bytes(R, Cc))
+
+    @staticmethod
+    def add(x, noise, strength, y, R, Cc, lrelu_alpha=1.0):
+        """y = LeakyReLU(x + strength[0] * noise[r]) over the rows of x [R, Cc]; ``strength`` is a device scalar; y may be x."""
+        _f32(x, noise, strength, y)
+        assert x.numel() == R * Cc == y.numel() and noise.numel() == R and strength.numel() == 1
+        check(_lib.load().bg_noise_add_f32(_ptr(x), _ptr(noise), _ptr(strength), _ptr(y), R, Cc, lrelu_alpha, _stream()), "bg_noise_add_f32")
+        return y
+
+    @staticmethod
+    def grad(dz, noise, dstrength, R, Cc, ws, beta=0.0, scale=1.0):
+        """dstrength[0] = beta * old + scale * sum_r noise[r] * sum_c dz[r, c]: two launches, a fixed order, the same bits every run."""
+        _f32(dz, noise, dstrength)
+        assert dz.numel() == R * Cc and noise.numel() == R and dstrength.numel() == 1
+        assert ws is not None and ws.numel() * ws.element_size() >= _lib.load().bg_noise_grad_workspace_bytes(R, Cc), "noise.grad: workspace too small"
+        check(_lib.load().bg_noise_grad_f32(_ptr(dz), _ptr(noise), _ptr(dstrength), R, Cc, _ptr(ws), beta, scale, _stream()), "bg_noise_grad_f32")
+        return dstrength
+
+
 # ------------------------------------------------------------------ differentiable augmentation (include/bgan.h)
 class diffaug:
     """The DiffAugment kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's public
@@ -1027,6 +1062,19 @@ def uniform(out, seed, offset=0, counter=None):
     offset = _draw_offset(out, offset, counter)
     check(_lib.load().bg_uniform_f32(_ptr(out), out.numel(), seed, offset, _stream()), "bg_uniform_f32")
     return out
+
+
+class rng:
+    """Draws beyond the reference's two.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's
+    public functions by name; these calls are recorded by the noise tests' own recorder."""
+
+    @staticmethod
+    def normal(out, seed, offset=0, counter=None):
+        """N(0, 1) draws (bg_normal_f32): the layout contract, offset and counter of ``uniform``; Box-Muller inside a Philox block."""
+        _f32(out)
+        offset = _draw_offset(out, offset, counter)
+        check(_lib.load().bg_normal_f32(_ptr(out), out.numel(), seed, offset, _stream()), "bg_normal_f32")
+        return out
 
 
 def keep_mask(out, keep_prob, seed, offset=0, counter=None):

@@ -107,8 +107,11 @@ class WGAN:
                  config: TrainingConfig, *args, reproduce_vector_loss_quirk: bool = True, sync_metrics: bool = True,
                  sync_batchnorm: bool = True, merge_critic_passes: bool = True, gp_zero_norm_guard: bool = False,
                  merge_gp_filter_gradients: bool = True, step_replay: bool = True, persistent_input: bool = False,
-                 conv_math: str = "fp32", generator_ema=None, augment=None, objective=None, **kwargs):
+                 conv_math: str = "fp32", generator_ema=None, augment=None, objective=None, latent_distribution: str = "uniform",
+                 **kwargs):
         ops.conv_math_code(conv_math)        # ValueError before anything is built
+        if latent_distribution not in ("uniform", "normal"):
+            raise ValueError(f"latent_distribution must be 'uniform' or 'normal', got {latent_distribution!r}")
         augment = diffaugment.as_augment(augment)      # ValueError likewise
         ema_schedule = ema_mod.as_schedule(generator_ema)      # ValueError likewise
         objective = objective_mod.as_objective(objective, self.uses_gradient_penalty)      # ValueError likewise
@@ -144,6 +147,9 @@ class WGAN:
             raise NotImplementedError("PixelNormalization in the discriminator: the layer is the generator's normalisation; a critic with "
                                       "it has no gradient-penalty route (PixelNormalization in a critic under the gradient penalty is not "
                                       "built)")
+        if any(l.kind == "noise" for l, _ in self.discriminator.flat_layers()):
+            raise NotImplementedError("NoiseInjection in the discriminator: the layer is the generator's noise input; a critic with it "
+                                      "has no gradient-penalty route (NoiseInjection in a critic under the gradient penalty is not built)")
         self.discriminator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.d_steps_per_g_step = self.hparams.d_steps_per_g_step
         self.batch_size = None
@@ -187,6 +193,10 @@ class WGAN:
         self._rng_off = 0
         self._bufs = {}
         self._injected = None
+        # the latents' distribution: "uniform" on [0, 1) (the reference's tf.random.uniform, wgan.py:118) or "normal", N(0, I) (the
+        # draw the ProGAN / StyleGAN papers take; with it normalize_latents=True normalises what they normalise).  Either comes from
+        # the model's own stream and counter, one launch per draw
+        self.latent_distribution = latent_distribution
         # weight averaging (ema.py): None / a decay / a GeneratorEMA.  generator_ema is the averaged model -- the generator's
         # structure in its own ParamStore, bit-copies of the live weights and BatchNorm statistics now -- and generator_step
         # updates it with one launch after the optimizer; generate_samples(ema=True) runs it.  Off: nothing is allocated or launched
@@ -305,8 +315,31 @@ class WGAN:
         ops.uniform(out, self._rng_seed + 7919 * dist.rank(), counter=(self, "_rng_off"))
         return out
 
+    def _latents(self, name, shape):
+        """A batch of latents from the model's own stream, in the model's ``latent_distribution``."""
+        if self.latent_distribution == "uniform":
+            return self._uniform(name, shape)
+        out = self._buf(name, shape)
+        ops.rng.normal(out, self._rng_seed + 7919 * dist.rank(), counter=(self, "_rng_off"))
+        return out
+
     def _inj(self, key):
         return None if self._injected is None else self._injected.get(key)
+
+    def _noise_seed(self):
+        """The seed of the noise maps a generator with NoiseInjection layers draws in its forwards: the generator network's own
+        counter (``generator.net().rng_offset``) under a seed that differs per rank -- every replica sees its own noise -- and from
+        the seeds of the critic's Dropout masks (104729 * (rank + 1)) and of the model's own stream (7919 * rank)."""
+        return self._rng_seed + 15485863 * (dist.rank() + 1)
+
+    def _noise_args(self, G, noise):
+        """The keywords a forward of generator network ``G`` takes for its noise maps (none without NoiseInjection layers: such a
+        forward is called as it always was).  ``noise``: None (drawn), maps [B, P], or False (left out)."""
+        if not G.has_noise:
+            return {}
+        if noise is not None and noise is not False:
+            noise = self._as_device(noise)
+        return dict(seed=self._noise_seed(), noise=noise)
 
     def _aug_params(self, name, keys, B):
         """(DiffAugment, params [len(keys) * B, 8]) for one pass of the critic, or None without augmentation: ONE draw from the
@@ -335,10 +368,15 @@ class WGAN:
     def train_on_batch(self, reals, *args, randomness=None, **kwargs):
         """wgan.py:86-114.  ``randomness`` (build-side, for parity tests) injects the step's random inputs:
         dict(z_d, z_g, alpha, mask_fake, mask_real) and, with ``augment``, the [B, 8] uniforms aug_fake, aug_real, aug_hat (D-step)
-        and aug_g (G-step); [B, 12] with an AdaptiveAugment (columns 8..10: the gates of colour, translation, cutout)."""
+        and aug_g (G-step); [B, 12] with an AdaptiveAugment (columns 8..10: the gates of colour, translation, cutout); with a generator
+        that has NoiseInjection layers noise_d / noise_g, the [B, P] noise maps of its forward in the D-step / G-step (per sample,
+        the layers' maps in network order; P = generator.net().noise_pixels)."""
         self.reset_metrics()
         reals = self._as_device(reals)
         self.batch_size = int(reals.shape[0])
+        if randomness is not None and not self.generator.net().has_noise and any(k in randomness for k in ("noise_d", "noise_g")):
+            raise ValueError("randomness: noise_d / noise_g are the noise maps of a generator with NoiseInjection layers; this generator "
+                             "has none")
         self._injected = randomness
         self._defer_metrics = True
         for model in (self.generator, self.discriminator):
@@ -423,7 +461,10 @@ class WGAN:
                self._optimizer_key(self.generator), self._optimizer_key(self.discriminator),
                # with penalty_interval k > 1 the critic steps with and without penalty are two programs that alternate and both
                # replay; the generator's step does not depend on the phase
-               ("objective", self._objective.static_config(), self._penalty_this_step() if kind == "d" else None))
+               ("objective", self._objective.static_config(), self._penalty_this_step() if kind == "d" else None),
+               # the latents' draw is another kernel.  (A generator with NoiseInjection layers needs no field: the layers are fixed
+               # at construction, a program belongs to one model, and n_train differs from the same stack without them)
+               self.latent_distribution)
         if self.generator_ema is not None:
             # the averaged model's presence, the two buffers the update writes and the schedule's static configuration: a program
             # recorded without the average, or on other buffers, never replays
@@ -500,11 +541,12 @@ class WGAN:
 
     def latents_batch(self):
         assert self.batch_size is not None
-        return self._uniform("latents", (self.batch_size, self.latent_size))
+        return self._latents("latents", (self.batch_size, self.latent_size))
 
-    def generate_samples(self, latents=None, training=False, ema=False):
+    def generate_samples(self, latents=None, training=False, ema=False, noise=None):
         """``ema=True``: the averaged generator (``generator_ema=`` of the constructor), inference BatchNorm on its own averaged
-        moving statistics."""
+        moving statistics.  ``noise`` (a generator with NoiseInjection layers): None draws fresh noise maps, a [B, P] tensor gives
+        them, False leaves the noise out (engine.Net.forward)."""
         if ema and self.generator_ema is None:
             raise ValueError("generate_samples(ema=True): this model has no averaged generator (construct it with generator_ema=...)")
         if ema and training:
@@ -516,7 +558,7 @@ class WGAN:
         latents = self._as_device(latents)
         G = (self.generator_ema if ema else self.generator).net()
         ctx = G.context(int(latents.shape[0]), "g")
-        return G.forward(ctx, latents, training=training)
+        return G.forward(ctx, latents, training=training, **self._noise_args(G, noise))
 
     # ---- discriminator
     def discriminator_loss(self, reals, fakes, real_scores, fake_scores):
@@ -540,8 +582,8 @@ class WGAN:
         D.check_rows(B)             # MinibatchStdDev: the slices of every pass of this step hold whole groups
         D.spectral_update()         # a spectrally normalised critic: its power round, before any forward of this step
         z = self._inj("z_d")
-        z = self._as_device(z) if z is not None else self._uniform("z_d", (B, self.latent_size))
-        fakes = G.forward(G.context(B, "g_dstep"), z, training=False)           # Q4: inference BN in the D-step
+        z = self._as_device(z) if z is not None else self._latents("z_d", (B, self.latent_size))
+        fakes = G.forward(G.context(B, "g_dstep"), z, training=False, **self._noise_args(G, self._inj("noise_d")))           # Q4: inference BN in the D-step
         # one draw for every row of the step's critic passes: fakes, reals and (with the penalty) x-hat, each with its own rows
         # penalty: this step carries the gradient penalty.  A WGANGP between two penalty steps of a lazy objective takes the
         # two-slice path of the plain WGAN -- no x-hat, no first or second order, no alpha or aug_hat draw -- with its own drift
@@ -695,10 +737,10 @@ class WGAN:
         G, D = self.generator.net(), self.discriminator.net()
         G.spectral_update()         # a spectrally normalised generator: its power round
         z = self._inj("z_g")
-        z = self._as_device(z) if z is not None else self._uniform("z_g", (B, self.latent_size))
+        z = self._as_device(z) if z is not None else self._latents("z_g", (B, self.latent_size))
         cg = G.context(B, "g")
         G.sync_bn = self.sync_batchnorm
-        fakes = G.forward(cg, z, training=True)
+        fakes = G.forward(cg, z, training=True, **self._noise_args(G, self._inj("noise_g")))
         chat = D.context(B, "hat")
         s = D.forward(chat, fakes, training=False, augment=self._aug_params("aug_g", ("aug_g",), B)).view(B)
         ds = self._buf("ds_g", (B,))

@@ -30,11 +30,13 @@ class DCGANGenerator(layers.SpectralSequential):
     """demo_celeba.py:51-93."""
 
     def __init__(self, latent_size=100, *args, upsampling="transpose", spectral_norm=False, normalization="batch", normalize_latents=False,
-                 equalized_lr=False, resample_kernel=(1, 3, 3, 1), **kwargs):
+                 equalized_lr=False, resample_kernel=(1, 3, 3, 1), noise=False, **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
+        if noise and normalization != "pixel":
+            raise ValueError("noise=True needs normalization='pixel': a NoiseInjection cannot stand in a BatchNormalization stage")
         self.latent_size = latent_size
         resize = {"transpose": None, "resize": layers.UpSampling2D,
                   "filtered": lambda: layers.FilteredUpSampling2D(resample_kernel)}[upsampling]
@@ -43,6 +45,8 @@ class DCGANGenerator(layers.SpectralSequential):
         def block(reshape=None):      # behind a linear layer: the reference's BatchNormalization -> LeakyReLU, or LeakyReLU -> PixelNormalization
             if pixel and reshape:
                 self.add(layers.Reshape(reshape))
+            elif noise:                 # StyleGAN's per-pixel noise input, behind every hidden (transposed) convolution
+                self.add(layers.NoiseInjection())
             if not pixel:
                 self.add(layers.BatchNormalization())
             self.add(layers.LeakyReLU())
@@ -134,6 +138,12 @@ def make_parser():
                              "and the hidden convolutions then carry a bias)")
     parser.add_argument("--normalize-latents", dest="normalize_latents", action="store_true",
                         help="a PixelNormalization of the latent vectors in front of the generator's Dense")
+    parser.add_argument("--generator-noise", dest="generator_noise", action="store_true",
+                        help="StyleGAN's per-pixel noise inputs: a NoiseInjection (strength * N(0, 1) per pixel, one learned strength per "
+                             "layer, initialised to zero) behind every hidden convolution of the generator (needs --generator-norm pixel)")
+    parser.add_argument("--latent-distribution", dest="latent_distribution", default="uniform", choices=["uniform", "normal"],
+                        help="the latents' distribution: uniform on [0, 1) (default, the reference's) or N(0, I) (the ProGAN / StyleGAN "
+                             "papers'; what --normalize-latents is meant to normalise)")
     parser.add_argument("--generator-spectral-norm", dest="generator_spectral_norm", action="store_true",
                         help="spectral normalisation of every Dense, Conv2DTranspose and Conv2D of the generator (not together with "
                              "the generator average)")
@@ -198,7 +208,7 @@ def main(argv=None):
     config.checkpoint_dir = config.log_dir + "/checkpoints"
     gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
                          normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr,
-                         resample_kernel=args.resample_kernel)
+                         resample_kernel=args.resample_kernel, noise=args.generator_noise)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
                               minibatch_stddev=args.critic_mbstd, equalized_lr=args.critic_equalized_lr, resample_kernel=args.resample_kernel)
     generator_ema = None
@@ -208,6 +218,7 @@ def main(argv=None):
         generator_ema = GeneratorEMA(halflife_images=args.g_ema_halflife_images)
     gan = blurred_gan.BlurredWGANGP(gen, disc, hyperparams=hyperparameters, config=config, conv_math=args.conv_math,
                                     generator_ema=generator_ema, persistent_input=bool(args.dataset), augment=blurred_gan.diffaugment.augment_from_args(args),
+                                    latent_distribution=args.latent_distribution,
                                     objective=blurred_gan.Objective(args.loss, args.penalty_target, args.penalty_on, args.penalty_interval))
     manager = CheckpointManager(gan, directory=config.checkpoint_dir, max_to_keep=5)
     if manager.latest_checkpoint:

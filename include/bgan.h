@@ -310,6 +310,26 @@ int bg_pixelnorm_fwd_f32(const float* x, float* y, float* r /* may be NULL */, i
 /* dz as above.  dz may alias g where the call's route has chunks == 1; it must not alias y (BG_ERR_UNSUPPORTED). */
 int bg_pixelnorm_bwd_f32(const float* g, const float* y, const float* r, float* dz, int R, int C, float lrelu_alpha, void* stream);
 
+/* ---- noise inputs (Karras et al. 2019 / 2020; layers.NoiseInjection) + the LeakyReLU behind them, fp32 ------------------------
+ * What a StyleGAN2 synthesis layer does between its convolution and its activation: it draws one N(0, 1) value per pixel of the
+ * map, multiplies it by ONE learned scalar, the layer's noise strength (initialised to zero), adds the product to every channel of
+ * that pixel, and then applies the bias / LeakyReLU.  Data is [R, C]: R = B * H * W rows (pixels of NHWC maps) of C contiguous
+ * channels; noise is [R]; strength is one float in DEVICE memory (a trainable variable; a replayed step program sees its current
+ * value).
+ *   forward   t_r = strength[0] * noise[r] (rounded to fp32 once),  y[r, c] = a > 0 ? a : lrelu_alpha * a  with a = x[r, c] + t_r
+ *             (lrelu_alpha = 1: no activation).  y may alias x.  No LDS.
+ *   gradient  dstrength[0] = beta * old + scale * sum_r noise[r] * (sum_c dz[r, c])   (beta = 0: old is not read), dz the
+ *             gradient at a.  Deterministic: a row's channel sum, a workgroup's sum and the finish run in a fixed order, no
+ *             atomics, two launches, dz read once.  ws: bg_noise_grad_workspace_bytes(R, C) bytes of device scratch.
+ * Any R, C >= 1.  Pointers 4-byte aligned (BG_ERR_BAD_ALIGNMENT).  A call moves float4s where C % 4 == 0 and x, y (dz) are 16-byte
+ * aligned, single floats otherwise; no call is refused for a misaligned view.  bg_noise_route (host only): the eight ints of
+ * bg_pixelnorm_route, for these kernels.  A refused call launches nothing.  No call takes a step-program binding. */
+#define BG_NOISE_ROUTE_INTS 8
+int bg_noise_route(int C, int* out);
+int bg_noise_add_f32(const float* x, const float* noise, const float* strength, float* y, int R, int C, float lrelu_alpha, void* stream);
+size_t bg_noise_grad_workspace_bytes(int R, int C);
+int bg_noise_grad_f32(const float* dz, const float* noise, float* dstrength, int R, int C, void* ws, float beta, float scale, void* stream);
+
 /* ---- differentiable augmentation (DiffAugment, Zhao et al. 2020) of the critic's input, NHWC fp32 -----------------------------
  * Per sample an affine map T(x) = L x + k of its [H, W, C] map: colour, then translation, then cutout.  ops_mask: bit 0 colour,
  * bit 1 translation, bit 2 cutout; an absent operation takes its neutral value and does no arithmetic (without colour values are
@@ -667,6 +687,14 @@ int bg_ema_f32(float* avg, const float* theta, size_t n, float* avg2, const floa
 /* ---- RNG: tf.random.uniform (wgan.py:118,237) and Dropout masks; counter-based, own stream ---- */
 int bg_uniform_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint64_t offset, void* stream);
+/* N(0, 1) draws (the per-pixel noise inputs of a StyleGAN synthesis layer, and latents drawn from N(0, I)).  The layout contract of
+ * the two draws above: element e comes from the Philox4x32-10 block with counter offset + e / 4, and a draw consumes (n + 3) / 4
+ * blocks; the third counter word is 2 (0: the uniforms, 1: the keep masks).  Box-Muller inside a block: words (0, 1) give elements
+ * (0, 1), words (2, 3) give elements (2, 3); u1 = ((w_a >> 8) + 1) * 2^-24 in (0, 1], u2 = (w_b >> 8) * 2^-24 in [0, 1),
+ * r = sqrtf(-2 logf(u1)), and the two elements are r * cospi(2 u2) and r * sinpi(2 u2) by the accurate library functions.
+ * |z| <= 5.77 by construction; u1 = 1 gives an exact 0.  Any n > 0 and any 4-byte aligned out; nothing is written outside
+ * [0, n).  Takes BG_BIND_RNG_OFFSET as bg_uniform_f32 does. */
+int bg_normal_f32(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream);
 
 /* ---- step programs: the step-level entry points of SURVEY.md 8b (bg_dstep / bg_gstep) -----------------------------------
  * The reference runs one Python pass over its TF ops per batch (wgan.py:86-114: discriminator_step :132-151, generator_step
@@ -696,7 +724,7 @@ int bg_keep_mask_u8(uint8_t* out, size_t n, float keep_prob, uint64_t seed, uint
  * bg_program_record_end: a silently dropped one would replay the recording step's value for ever. */
 typedef struct bg_program bg_program;
 #define BG_BIND_ADAM_LR 1     /* bg_adam_f32: lr_t <- (float) slots_f64[slot]                         */
-#define BG_BIND_RNG_OFFSET 2  /* bg_uniform_f32, bg_keep_mask_u8: offset <- slots_u64[slot]            */
+#define BG_BIND_RNG_OFFSET 2  /* bg_uniform_f32, bg_keep_mask_u8, bg_normal_f32: offset <- slots_u64[slot] */
 #define BG_BIND_OPT_LR 3      /* bg_sgd_f32, bg_rmsprop_f32: lr, bg_adam_amsgrad_f32: lr_t <- (float) slots_f64[slot] */
 #define BG_BIND_EMA_W 4       /* bg_ema_f32: w <- (float) slots_f64[slot]                              */
 int bg_program_create(bg_program** out, int n_slots);
