@@ -86,6 +86,14 @@ SIGNATURES = {
     "bg_noise_add_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "bg_noise_grad_workspace_bytes": (_z, [_i, _i]),
     "bg_noise_grad_f32": (_i, [_p, _p, _p, _i, _i, _p, _f, _f, _p]),
+    "bg_mod_scale_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
+    "bg_mod_dot_plan": (_i, [_i, _i, _i, C.POINTER(_i)]),
+    "bg_mod_dot_workspace_bytes": (_z, [_i, _i, _i]),
+    "bg_mod_dot_f32": (_i, [_p, _p, _p, _i, _i, _i, _p, _z, _f, _f, _p]),
+    "bg_mod_wsq_f32": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "bg_mod_wsq_grad_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
+    "bg_mod_demod_f32": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
+    "bg_mod_demod_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "bg_diffaug_plan": (_i, [_i, _i, _i, _i, _i] + [C.POINTER(_i)] * 5),
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
@@ -172,6 +180,7 @@ SIGNATURES = {
 COMM_ID_BYTES = 128
 PIXELNORM_ROUTE_INTS = 8       # include/bgan.h BG_PIXELNORM_ROUTE_INTS
 NOISE_ROUTE_INTS = 8           # include/bgan.h BG_NOISE_ROUTE_INTS
+MOD_DOT_PLAN_INTS = 8          # include/bgan.h BG_MOD_DOT_PLAN_INTS
 MBSTD_PLAN_INTS = 12          # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 EQLR_DESC_INTS = 12            # include/bgan.h BG_EQLR_DESC_INTS

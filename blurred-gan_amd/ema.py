@@ -15,7 +15,7 @@ from __future__ import annotations
 import copy
 import numbers
 
-from .layers import EqualizedLearningRate, Sequential, SpectralNormalization
+from .layers import EqualizedLearningRate, Sequential, SpectralNormalization, StyleModulation
 
 __all__ = ["GeneratorEMA", "clone_structure"]
 
@@ -89,11 +89,14 @@ def _clone_layer(layer):
     # the copy starts from the live layer's CURRENT values: ParamStore copies a variable it finds in `vars` and draws from the
     # weight-initialisation RNG only for one it does not find, and it rebinds the COPY's dict, never the live layer's
     c.vars = dict(layer.vars)
-    if isinstance(layer, (SpectralNormalization, EqualizedLearningRate)):
-        # a wrapper shares ONE dict with the layer it wraps: the copy gets an inner layer of its own, bound to the copy's dict
-        # (a shallow copy alone would leave the clone's inner layer on the live model's variables)
-        c.layer = copy.copy(layer.layer)
-        c.layer.vars = c.vars
+    w = c
+    while isinstance(w, (SpectralNormalization, EqualizedLearningRate, StyleModulation)):
+        # a wrapper shares ONE dict with the layer it wraps (a StyleModulation around an EqualizedLearningRate: all three): the copy
+        # gets inner layers of its own, bound to the copy's dict (a shallow copy alone would leave the clone's inner layer on the
+        # live model's variables)
+        w.layer = copy.copy(w.layer)
+        w.layer.vars = c.vars
+        w = w.layer
     if isinstance(layer, Sequential):
         c.layers = [_clone_layer(l) for l in layer.layers]
         c._store = c._net = c.optimizer = None

@@ -32,7 +32,7 @@ import torch
 
 from . import dist, ops
 from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_LRELU
-from .layers import EqualizedLearningRate, SpectralNormalization
+from .layers import MOD_RULE, EqualizedLearningRate, SpectralNormalization, StyleModulation
 
 
 RESAMPLE = ("upsample", "avgpool", "firup", "firdown")      # "fir*": the FIR-filtered pair (layers.Filtered*Sampling2D)
@@ -52,6 +52,7 @@ class Stage:
         self.pn = None              # layers.PixelNormalization directly behind the stage's LeakyReLU (the generator's normalisation)
         self.pn_channels = None     # the C it normalises over: the last axis of the map at the layer (a Dense's, behind its Reshape)
         self.noise = None           # layers.NoiseInjection directly behind the stage's Conv2D / Conv2DTranspose (the generator's noise input)
+        self.mod = lin if isinstance(lin, StyleModulation) else None      # layers.StyleModulation: the stage's conv is modulated by the styles
         self.act = getattr(lin, "activation", None)
         self.alpha = 1.0
         self.drop = None
@@ -84,6 +85,11 @@ class Stage:
     def ln_pixels(self):
         """Rows of an LN stage's [R, C] view per sample: its map's pixels."""
         return int(np.prod(self.out_shape[:-1]))
+
+    @property
+    def mod_pixels(self):
+        """(P_in, P_out) of a modulated stage: the pixels per sample of its input and of its output map."""
+        return int(np.prod(self.in_shape[:-1])), int(np.prod(self.out_shape[:-1]))
 
     @property
     def noise_pixels(self):
@@ -132,7 +138,8 @@ class Context(_StageBuffers):
             self.a.append(f(B, *st.out_shape))
             self.dz.append(None)
             self.v.append(None)
-            self.z.append(f(B, *st.out_shape) if st.bn is not None or st.ln is not None or st.pn is not None else None)
+            self.z.append(f(B, *st.out_shape) if st.bn is not None or st.ln is not None or st.pn is not None
+                          or (st.mod is not None and st.mod.demodulate) else None)
             c = B * st.ln_pixels if st.ln is not None else B * st.pn_rows if st.pn is not None else st.out_shape[-1]
             self.mean.append(f(c) if st.bn is not None or st.ln is not None else None)
             self.inv.append(f(c) if st.bn is not None or st.ln is not None or st.pn is not None else None)      # PixelNormalization: the rows' r
@@ -163,6 +170,14 @@ class Context(_StageBuffers):
                 if st.noise is not None:
                     self.noise[i] = self.noise_flat[o:o + B * st.noise_pixels]
                     o += B * st.noise_pixels
+        # StyleModulation stages: the styles s [B, I], the demodulation d [B, O] and the modulated input xs of the pass (the raw
+        # conv output is z[i]); w is the pass's style source, the assembled input behind latent_pn
+        self.mod_w = None
+        self.mod_s, self.mod_d, self.mod_xs = ([None] * len(net.stages) for _ in range(3))
+        for i, st in enumerate(net.stages):
+            if st.mod is not None:
+                self.mod_s[i], self.mod_xs[i] = f(B, st.in_shape[-1]), f(B, *st.in_shape)
+                self.mod_d[i] = f(B, st.out_shape[-1]) if st.mod.demodulate else None
         self._net, self._device = net, device
         net.check_rows(B)
         self._extra = {}
@@ -249,6 +264,16 @@ class Context(_StageBuffers):
             self._extra["blur_grad"] = torch.empty_like(self.a0)
         return self._extra["blur_grad"]
 
+    def mod_scratch(self, i):
+        """(dd [B, O], dq [B, O], ds [B, I], s2 [B, I], dQ [I, O]) of modulated stage i's backward."""
+        key = ("mod", i)
+        if key not in self._extra:
+            st = self._net.stages[i]
+            I, O = st.in_shape[-1], st.out_shape[-1]
+            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=self._device)
+            self._extra[key] = (f(self.B, O), f(self.B, O), f(self.B, I), f(self.B, I), f(I, O))
+        return self._extra[key]
+
     def input_grad(self):
         if self.din is None:
             self.din = torch.empty((self.B,) + self._net.in_shape, dtype=torch.float32, device=self._device)
@@ -329,6 +354,9 @@ class Net:
                         raise NotImplementedError(self.PN_RULE + " (MinibatchStdDev behind a PixelNormalization stage is not supported)")
                 cur = Stage(l, s)
                 self.stages.append(cur)
+                if cur.mod is not None: self.mod_place(flat_layers, idx, cur)      # noqa: E701
+            elif k in ("bn", "layernorm", "dropout", "pixelnorm") and cur is not None and cur.mod is not None:
+                raise NotImplementedError(MOD_RULE + f" (a {type(l).__name__} in the stage of a StyleModulation)")
             elif k == "pixelnorm":
                 self.pn_place(flat_layers, idx, cur)
             elif k in ("bn", "layernorm", "dropout", "lrelu") and cur is not None and cur.pn is not None:
@@ -384,11 +412,11 @@ class Net:
         # buffer, which spectral_update() fills; the plain conv layers keep their batched transpose
         self.spectral_layers = [st.lin for st in self.stages if isinstance(st.lin, SpectralNormalization)]
         # layers.EqualizedLearningRate: c * W (and its transposed copy) likewise, filled by eqlr_update()
-        self.eqlr_layers = [st.lin for st in self.stages if isinstance(st.lin, EqualizedLearningRate)]
+        self.eqlr_layers = [l for l in (self.weight_layer(st.lin) for st in self.stages) if isinstance(l, EqualizedLearningRate)]
         if self.spectral_layers and self.eqlr_layers:
             raise NotImplementedError("SpectralNormalization and EqualizedLearningRate layers in one model are not supported: both lay "
                                       "out the store's effective-weight buffer")
-        self.plain_conv_layers = [l for l in self.conv_layers if not isinstance(l, (SpectralNormalization, EqualizedLearningRate))]
+        self.plain_conv_layers = [l for l in self.conv_layers if not isinstance(self.weight_layer(l), (SpectralNormalization, EqualizedLearningRate))]
         # power rounds per optimizer step, read ONCE here (0: no wrapped layer): part of the step-program key; changing a layer's
         # power_iterations on a built model has no effect
         rounds = {l.power_iterations for l in self.spectral_layers}
@@ -403,6 +431,8 @@ class Net:
         self.has_pn = self.latent_pn is not None or any(st.pn is not None for st in self.stages)
         self.has_noise = any(st.noise is not None for st in self.stages)
         self.noise_pixels = sum(st.noise_pixels for st in self.stages if st.noise is not None)     # P: noise values per sample
+        self.mod_layers = [st.lin for st in self.stages if st.mod is not None]
+        self.has_mod = bool(self.mod_layers)
         self._ctx = {}
         self._rows_checked = set()
         self._ws = None
@@ -466,6 +496,7 @@ class Net:
         self.spectral_update(iterate=False)
         self.eqlr_update()
         self.store.refresh_transposed(self.plain_conv_layers)
+        self.mod_update()
 
     # ---- spectral normalisation (DESIGN.md §5 "Spectral normalisation").  Public names, as the LayerNormalization helpers below:
     # the engine-trace fixture's configurations have no such layer; tests/test_spectral_cpu.py records what these enqueue.
@@ -570,6 +601,7 @@ class Net:
         ctx.aug = augment
         if augment is not None: x = self.aug_forward(ctx, x)      # noqa: E701
         if self.latent_pn is not None: x = self.pn_latents(ctx, x)      # noqa: E701
+        if self.has_mod: ctx.mod_w = x.view(ctx.B, *self.in_shape)      # noqa: E701  (the style source of every modulated stage)
         ctx.dropout_active = bool(training)
         # one launch draws the masks of all stages; where their rates differ, or masks are handed in, each stage sets its own
         one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
@@ -641,6 +673,7 @@ class Net:
         BatchNorm + LeakyReLU pass where it has one of its own."""
         if st.ln is not None: return self.ln_forward(ctx, i, st, xin, out)      # noqa: E701
         if st.pn is not None: return self.pn_forward(ctx, i, st, xin, out)      # noqa: E701
+        if st.mod is not None: return self.mod_forward(ctx, i, st, xin, out)      # noqa: E701
         if st.noise is not None and ctx.noise_active: return self.noise_forward(ctx, i, st, xin, out)      # noqa: E701
         bias = st.lin.vars.get("bias")
         tgt = ctx.z[i] if st.bn is not None else out
@@ -758,6 +791,7 @@ class Net:
         and Dense gradients are still taken here).  ``keep_u_rows`` = (lo, hi): LayerNormalization stages keep u, the gradient at
         their normalised pre-activation, for those samples (the x-hat rows: gp_second_order's source term needs it)."""
         if need_dx and self.latent_pn is not None: raise NotImplementedError("the gradient at the input of a network that starts with a PixelNormalization (the latents' normalisation has no backward)")  # noqa: E701
+        if need_dx and self.has_mod: raise NotImplementedError("the gradient at the input of a network with StyleModulation stages (dL/dw, the gradient through the styles, is not built)")  # noqa: E701
         if need_dw:
             self.store.ensure_opt_state()
         p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active(),
@@ -768,6 +802,7 @@ class Net:
             prev = self.stages[i - 1] if i > 0 else None
             has_dw = need_dw and st.kind not in PARAMETER_FREE
             dz = ctx.dz[i] = self._grad_through_activation(p, i, st, g.view(ctx.B, *st.out_shape), g_is_dz)
+            if st.mod is not None: g, g_is_dz = self.mod_backward(p, i, st, dz); continue      # noqa: E701,E702
             # SyncBN with a BatchNorm stage below: the data gradient goes FIRST, the lower stage's backward statistics are
             # reduced and their all-reduce is put in flight, and only then this stage's filter gradient runs -- the small
             # latency-bound collective hides behind an MFMA kernel instead of sitting on the critical path of every layer.
@@ -1026,6 +1061,101 @@ class Net:
         R, Cc = p.dw_rows * st.noise_pixels, st.out_shape[-1]
         return ops.noise.grad(dzw, p.ctx.noise[i][:R], g, R, Cc, self.workspace(ops.noise.workspace_bytes(R, Cc)), beta=p.beta, scale=p.scale)
 
+    # ---- StyleModulation (DESIGN.md §5 "Style modulation").  Public names for the reason the LayerNormalization helpers carry them:
+    # no configuration of the engine-trace fixture has the layer; tests/test_modconv_cpu.py records what these enqueue.
+    MOD_RULE = MOD_RULE
+
+    @staticmethod
+    def weight_layer(lin):
+        """The layer that owns the derived weights of ``lin``: what a StyleModulation wraps (an EqualizedLearningRate keeps its c * W)
+        where it wraps a wrapper, else ``lin`` itself."""
+        return lin.layer if isinstance(lin, StyleModulation) and isinstance(lin.layer, EqualizedLearningRate) else lin
+
+    def mod_place(self, flat_layers, idx, cur):
+        """Net.__init__'s placement rule for the StyleModulation at ``flat_layers[idx]``, the linear layer of the new stage ``cur``:
+        the network's input is the [L] style vector and another stage stands in front; everything else is refused.  (What may
+        follow in the stage is checked as the layers arrive; what the wrapper may wrap, by the wrapper.)"""
+        if len(self.in_shape) != 1 or len(self.stages) < 2 or cur.mod.style_dim != self.in_shape[0]:
+            raise NotImplementedError(MOD_RULE + " (a first stage has no style source: the only one is the network's [L] input)")
+
+    def mod_geom(self, st):
+        """(taps, I, O, transposed) of modulated stage ``st``'s kernel: [k, k, I, O], or [k, k, O, I] for a Conv2DTranspose."""
+        return st.lin.k * st.lin.k, st.in_shape[-1], st.out_shape[-1], st.kind == "convT"
+
+    def mod_update(self):
+        """Q = sum over the taps of W_eff^2 of every demodulating layer, from the effective weights as they stand: one launch per
+        layer, where prepare_weights refreshes the other derived weights (not per pass)."""
+        for st in self.stages:
+            if st.mod is not None and st.mod.demodulate:
+                taps, I, O, tr = self.mod_geom(st)
+                ops.modconv.wsq(self.store.kernel(st.lin), self.store.mod_q(st.lin), taps, I, O, transposed=tr)
+
+    def mod_forward(self, ctx, i, st, xin, out):
+        """A modulated stage: s = w . A + a, xs = x * s, the conv on xs; with demodulation z is kept, d = 1 / sqrt((s * s) . Q + eps)
+        and out = LeakyReLU(d * z + bias), the stage's noise between the two where it has one; without, the conv writes out
+        through its own epilogue.  The same in training and in inference."""
+        B, v = ctx.B, st.lin.vars
+        (Pi, Po), I, O = st.mod_pixels, st.in_shape[-1], st.out_shape[-1]
+        s, xs = ctx.mod_s[i], ctx.mod_xs[i]
+        ops.gemm(ctx.mod_w, v["style_kernel"], s, B, I, self.in_shape[0], bias=v["style_bias"])
+        ops.modconv.scale(xin, s, xs, B, Pi, I)
+        if not st.mod.demodulate:
+            self._conv(st, xs, out, False, EPI_TANH if st.act == "tanh" else EPI_NONE)
+            return
+        z, d = ctx.z[i], ctx.mod_d[i]
+        self._conv(st, xs, z, False, EPI_NONE)
+        ops.modconv.demod(s, self.store.mod_q(st.lin), d, B, I, O, eps=st.mod.epsilon)
+        noisy = st.noise is not None and ctx.noise_active
+        ops.modconv.scale(z, d, out, B, Po, O, bias=v.get("bias"), lrelu_alpha=1.0 if noisy else st.alpha)
+        if noisy: self.noise_add(ctx, i, st, out, st.alpha)      # noqa: E701
+
+    def mod_backward(self, p, i, st, dy):
+        """Stage i's backward from ``dy``, the gradient at d * z + bias (the activation backward left it in the stage's dz buffer):
+        the bias and noise sums, dd = sum dy * z, dz = d * dy in place, the conv's two gradients on xs, ds = sum x * dxs, the
+        demodulation's share of ds and of dW_eff, dx = s * dxs, and the style variables' gradients from ds.  Returns (dx, False):
+        the stage below applies its own activation backward (ds needs the unmasked dxs, so nothing is fused into the data
+        gradient).  The stage's slice goes to the reducer at the end: its last writer is here."""
+        ctx, v = p.ctx, st.lin.vars
+        B, L = ctx.B, self.in_shape[0]
+        if p.dw_rows != B: raise NotImplementedError("weight gradients from a part of the batch through a StyleModulation stage")      # noqa: E701
+        (Pi, Po), I, O = st.mod_pixels, st.in_shape[-1], st.out_shape[-1]
+        s, xs, xin, demod = ctx.mod_s[i], ctx.mod_xs[i], ctx.xin[i], st.mod.demodulate
+        dd, dq, ds, s2, dQ = ctx.mod_scratch(i)
+        g = self.store.grad_of
+        dz = dy.view(B, *st.out_shape)
+        if demod:
+            d = ctx.mod_d[i]
+            if p.need_dw:
+                if st.noise is not None: self.noise_backward(p, i, st, dz)      # noqa: E701
+                if "bias" in v:
+                    ops.colsum(dz, g(st.lin, "bias"), B * Po, O, self.workspace(ops.colsum_workspace_bytes(B * Po, O)), beta=p.beta, scale=p.scale)
+                ops.modconv.dot(dz, ctx.z[i], dd, B, Po, O, self.mod_dot_ws(B, Po, O))
+            # in place, unless dy is the caller's own tensor (a last stage without activation)
+            dz = ops.modconv.scale(dz, d, ctx.buf(ctx.dz, i), B, Po, O)
+        if p.need_dw:
+            self._filter_grad(st, xs, dz, p.beta, p.scale)
+        below = ctx.gin if self.rereads_rows(self.stages[i - 1]) else ctx.dz
+        tgt = ctx.buf(below, i - 1).view(B, *st.in_shape)
+        self._conv(st, dz, tgt, True, EPI_NONE)
+        if p.need_dw:
+            ops.modconv.dot(xin, tgt, ds, B, Pi, I, self.mod_dot_ws(B, Pi, I))
+            if demod:
+                taps, _, _, tr = self.mod_geom(st)
+                ops.modconv.demod_bwd(d, dd, s, self.store.mod_q(st.lin), dq, ds, B, I, O)
+                ops.modconv.scale(s, s, s2, B, 1, I)
+                ops.gemm(s2, dq, dQ, I, O, B, transA=True)
+                ops.modconv.wsq_grad(self.store.kernel(st.lin), dQ, g(st.lin, "kernel"), taps, I, O, transposed=tr, scale=p.scale)
+            ops.gemm(ctx.mod_w, ds, g(st.lin, "style_kernel"), L, I, B, transA=True, beta=p.beta, scale=p.scale)
+            ops.colsum(ds, g(st.lin, "style_bias"), B, I, self.workspace(ops.colsum_workspace_bytes(B, I)), beta=p.beta, scale=p.scale)
+            if p.reducer is not None:
+                p.reducer.ready(*self._train_range(st))
+        ops.modconv.scale(tgt, s, tgt, B, Pi, I)
+        return tgt, False
+
+    def mod_dot_ws(self, B, P, Cc):
+        nb = ops.modconv.dot_workspace_bytes(B, P, Cc)
+        return self.workspace(nb) if nb else None
+
     # ---- DiffAugment in front of stage 0 (DESIGN.md §5 "Augmentation").  Public names for the reason the LayerNormalization helpers
     # carry them: the engine-trace fixture's configurations run without augmentation; tests/test_diffaug_cpu.py records these.
     def aug_forward(self, ctx, x):
@@ -1108,6 +1238,7 @@ class Net:
 
         Not with LayerNormalization stages: their source backward (gp_ln_source_backward) needs the x-hat rows of the activations
         this pass overwrites, so such a critic takes ``gp_second_order`` on ``ctx.rows(lo, hi)``."""
+        if self.has_mod: raise NotImplementedError("StyleModulation in a critic under the gradient penalty is not built")  # noqa: E701
         if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
         if self.has_noise: raise NotImplementedError("NoiseInjection in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()
@@ -1128,6 +1259,7 @@ class Net:
         A LayerNormalization stage is not piecewise linear: its tangent is gp_ln_stage's, and what the linearised forward's
         dependence on the stage's PRIMAL input adds goes down the network once more in gp_ln_source_backward.  That pass writes the
         last contribution to every layer up to the top-most such stage, so those layers' slices go to the reducer from there."""
+        if self.has_mod: raise NotImplementedError("StyleModulation in a critic under the gradient penalty is not built")  # noqa: E701
         if self.has_pn: raise NotImplementedError("PixelNormalization in a critic under the gradient penalty is not built")  # noqa: E701
         if self.has_noise: raise NotImplementedError("NoiseInjection in a critic under the gradient penalty is not built")  # noqa: E701
         kinds = self._gp_kinds()

@@ -321,6 +321,58 @@ class EqualizedLearningRate(Layer):
         return [("kernel", shape, True, normal)] + specs[1:]         # the bias keeps its zeros
 
 
+MOD_RULE = ("StyleModulation wraps a Conv2D, a Conv2DTranspose or an EqualizedLearningRate around one of them (not a Dense, not a "
+            "SpectralNormalization in either nesting), in a generator whose input is the [L] style vector and behind at least one other "
+            "stage, in a stage without BatchNormalization, LayerNormalization, PixelNormalization or Dropout; demodulate=True not with "
+            "tanh, demodulate=False not with a bias")
+
+
+class StyleModulation(Layer):
+    """StyleGAN2's modulated convolution (Karras et al. 2020) around a Conv2D, a Conv2DTranspose or an EqualizedLearningRate around
+    one of them: a learned affine map of the network's input vector w [L] gives one style per input channel, s = w . style_kernel +
+    style_bias, which scales the layer's input map per sample; with ``demodulate`` the output is divided by the norm the scaled
+    weights would have, d = 1 / sqrt((s * s) . sum_taps W_eff^2 + epsilon), in place of a normalisation layer, and the bias follows.
+    The un-fused form of the paper: the activations are scaled, not the weights.  In a Sequential the wrapper stands for its layer,
+    as EqualizedLearningRate does: same kind, shapes, ``kernel`` and ``bias``; it adds the trainables ``style_kernel`` [L, I] (Glorot
+    uniform) and ``style_bias`` [I] (ones).  L is the model's input size, known once the wrapper is part of a model with an input
+    shape.  No mapping network, no gradient with respect to w (DESIGN.md section 5 "Style modulation")."""
+
+    def __init__(self, layer, demodulate=True, epsilon=1e-8, **kw):
+        inner = layer.layer if isinstance(layer, EqualizedLearningRate) else layer
+        if isinstance(layer, SpectralNormalization) or isinstance(inner, SpectralNormalization) or not isinstance(inner, (Conv2D, Conv2DTranspose)):
+            raise NotImplementedError(MOD_RULE + f" (got a {type(layer).__name__}"
+                                      + (f" around a {type(inner).__name__})" if inner is not layer else ")"))
+        if not float(epsilon) > 0.0:
+            raise ValueError(f"StyleModulation epsilon={epsilon!r}: must be positive")
+        self.demodulate, self.epsilon = bool(demodulate), float(epsilon)
+        if self.demodulate and inner.activation == "tanh":
+            raise NotImplementedError(MOD_RULE + " (demodulate=True in a stage with tanh)")
+        if not self.demodulate and inner.use_bias:
+            raise NotImplementedError(MOD_RULE + " (demodulate=False with a bias)")
+        kw.setdefault("input_shape", layer._declared_input_shape)
+        kw.setdefault("name", "style_modulation_" + layer.name)
+        super().__init__(**kw)
+        self.layer = layer
+        self.kind = layer.kind
+        self.style_dim = None       # L: set by the Sequential that holds the wrapper (flat_layers)
+        self.vars = layer.vars      # one set of variables, reachable through every object of the nesting
+
+    def __getattr__(self, name):    # what the wrapper does not have itself (filters, k, stride, activation, coefficient, ...) is the layer's
+        if name == "layer" or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.layer, name)
+
+    def out_shape(self, in_shape):
+        return self.layer.out_shape(in_shape)
+
+    def var_specs(self, in_shape):
+        if self.style_dim is None:
+            raise NotImplementedError(MOD_RULE + " (the model's input is no [L] vector: there is no style source)")
+        specs = list(self.layer.var_specs(in_shape))
+        L, I = int(self.style_dim), int(in_shape[-1])
+        return specs + [("style_kernel", (L, I), True, _glorot((L, I), L, I)), ("style_bias", (I,), True, _ones((I,)))]
+
+
 class LeakyReLU(Layer):
     kind = "lrelu"
 
@@ -613,6 +665,8 @@ class ParamStore:
         """The kernel the engine computes with: the layer's own variable (``transposed``: its [k*k][C][R] copy), or for a spectrally
         normalised layer W / sigma, for an equalised-learning-rate layer c * W, and its transposed copy in the effective-weight
         buffer."""
+        if isinstance(layer, StyleModulation) and isinstance(layer.layer, EqualizedLearningRate):
+            layer = layer.layer         # the wrapped EqualizedLearningRate owns c * W (engine.Net.eqlr_layers lists it)
         if isinstance(layer, SpectralNormalization):
             views = self._sn.get(id(layer))
             if views is None:
@@ -681,6 +735,17 @@ class ParamStore:
         ops.eqlr.check_table(table.host, self.theta.numel(), self.eff.numel())
         self._eq_table = (key, table)
         return table
+
+    def mod_q(self, layer):
+        """Q [I, O] = the sum over the taps of W_eff^2 of a demodulating StyleModulation layer: a derived weight like the transposed
+        copies, refreshed by engine.Net.mod_update(); one persistent buffer per layer (a recorded step program holds its address)."""
+        cache = self.__dict__.setdefault("_mod_q", {})
+        q = cache.get(id(layer))
+        if q is None:
+            w = layer.vars["kernel"]
+            I, O = (w.shape[3], w.shape[2]) if layer.kind == "convT" else (w.shape[2], w.shape[3])
+            q = cache[id(layer)] = torch.empty((I, O), dtype=torch.float32, device=self.device)
+        return q
 
     def transposed_kernel(self, layer):
         """[k*k][C][R] copy of a conv kernel stored [k*k][R][C]; refreshed after every optimiser step."""
@@ -774,6 +839,8 @@ class Sequential(Layer):
                 for ll, ss in l.flat_layers():
                     out.append((ll, ss))
             else:
+                if isinstance(l, StyleModulation):      # its style source is this model's input vector
+                    l.style_dim = int(self._in_shape[0]) if len(self._in_shape) == 1 else None
                 out.append((l, tuple(s)))
             s = l.out_shape(s)
         return out
@@ -870,6 +937,8 @@ class SpectralSequential(Sequential):
     equalized_lr = False
 
     def add(self, layer, gain=None):
+        if isinstance(layer, StyleModulation) and self.spectral_norm:
+            raise NotImplementedError(MOD_RULE + " (spectral_norm=True)")
         if isinstance(layer, (Conv2D, Conv2DTranspose, Dense)):
             if self.spectral_norm:
                 layer = SpectralNormalization(layer)

@@ -33,10 +33,17 @@ normalisation runs over the channels of the reshaped map.  The tanh output layer
 PixelNormalization in front of the Dense (with either normalisation).  Both combine with ``upsampling="resize"`` and
 ``spectral_norm=True``.
 
-``noise=True`` (the generator, with ``normalization="pixel"`` only; default False: the stack variable for variable as before) puts a
+``noise=True`` (the generator, with ``normalization="pixel"`` or ``"style"``; default False: the stack variable for variable as before) puts a
 ``layers.NoiseInjection`` behind every (transposed) convolution of the stack except the tanh output layer, in front of its LeakyReLU:
 StyleGAN's per-pixel noise inputs, one learned scalar ``noise_strength`` per layer, initialised to zero.  It combines with everything
 ``normalization="pixel"`` combines with.
+
+``normalization="style"`` (the generator) is StyleGAN2's: every hidden (transposed) convolution is a
+``layers.StyleModulation(conv, demodulate=True)`` with bias, then the NoiseInjection of ``noise=True``, then LeakyReLU -- no
+PixelNormalization; the tanh output layer is ``StyleModulation(conv, demodulate=False)``.  The Dense block is the one ``"pixel"``
+builds.  The styles come from the model's own input vector (behind the PixelNormalization of ``normalize_latents=True``): there is no
+mapping network.  Every modulated layer gains ``style_kernel`` [L, I] and ``style_bias`` [I].  It combines with ``noise=True``,
+``equalized_lr=True``, every ``upsampling=`` and ``normalize_latents=True``; ``spectral_norm=True`` is refused.
 
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
 engine computes with W / sigma, and every wrapped layer gains the non-trainable ``vector_u``, ``vector_v`` and ``sigma``.
@@ -46,6 +53,8 @@ learning rate): kernels drawn from N(0, 1), the engine computes with c * W, c = 
 front of a LeakyReLU, 1 for the tanh output layer and for the critic's Dense(1).  No new variables.  It combines with every other
 argument but ``spectral_norm=True`` (``ValueError``: W / sigma would cancel c)."""
 from __future__ import annotations
+
+import math
 
 from . import layers
 
@@ -72,16 +81,19 @@ class DCGANGenerator(layers.SpectralSequential):
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
             raise ValueError("equalized_lr=True together with spectral_norm=True: W / sigma cancels the run-time coefficient")
-        if noise and normalization != "pixel":
-            raise ValueError("noise=True needs normalization='pixel': a NoiseInjection cannot stand in a BatchNormalization stage")
+        if noise and normalization not in ("pixel", "style"):
+            raise ValueError("noise=True needs normalization='pixel' or 'style': a NoiseInjection cannot stand in a BatchNormalization stage")
         self.noise = bool(noise)
         if upsampling not in ("transpose", "resize", "filtered"):
             raise ValueError(f"upsampling must be 'transpose', 'resize' or 'filtered', got {upsampling!r}")
-        if normalization not in ("batch", "pixel"):
-            raise ValueError(f"normalization must be 'batch' or 'pixel', got {normalization!r}")
+        if normalization not in ("batch", "pixel", "style"):
+            raise ValueError(f"normalization must be 'batch' or 'pixel' (or 'style': modulated convolutions), got {normalization!r}")
+        if normalization == "style" and self.spectral_norm:
+            raise ValueError("normalization='style' together with spectral_norm=True: W / sigma under weight demodulation is not built")
         self.upsampling, self.normalization, self.normalize_latents = upsampling, normalization, bool(normalize_latents)
         self.resample_kernel = tuple(resample_kernel)
-        pixel = normalization == "pixel"
+        style = normalization == "style"
+        pixel = normalization == "pixel" or style       # "style" keeps the Dense block and the biases of "pixel"
         base, ch, convt, last = _G[arch]
         k = KSIZE.get(arch, 5)
         self.latent_size = latent_size or LATENT[arch]
@@ -103,23 +115,35 @@ class DCGANGenerator(layers.SpectralSequential):
         for filters, stride, act in convt:
             if stride == 2 and upsampling != "transpose":
                 self.add(layers.UpSampling2D() if upsampling == "resize" else layers.FilteredUpSampling2D(self.resample_kernel))
-                self.add(layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=pixel and act is None, activation=act))
+                conv = layers.Conv2D(filters, (k, k), strides=(1, 1), padding="same", use_bias=pixel and act is None, activation=act)
             else:
-                self.add(layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=pixel and act is None,
-                                                activation=act))
+                conv = layers.Conv2DTranspose(filters, (k, k), strides=(stride, stride), padding="same", use_bias=pixel and act is None,
+                                              activation=act)
+            self.add(self._modulated(conv) if style else conv)
             hw *= stride
             assert self.output_shape == (None, hw, hw, filters), self.output_shape
             if act is None and self.noise:
                 self.add(layers.NoiseInjection())
-            if act is None and pixel:
+            if act is None and style:
+                self.add(layers.LeakyReLU())
+            elif act is None and pixel:
                 self.add(layers.LeakyReLU())
                 self.add(layers.PixelNormalization())
             elif act is None:
                 self.add(layers.BatchNormalization())
                 self.add(layers.LeakyReLU())
         if last is not None:
-            self.add(layers.Conv2D(last, (k, k), padding="same", use_bias=False, activation="tanh"))
+            conv = layers.Conv2D(last, (k, k), padding="same", use_bias=False, activation="tanh")
+            self.add(self._modulated(conv) if style else conv)
         assert self.output_shape == (None,) + IMAGE_SHAPE[arch], self.output_shape
+
+    def _modulated(self, conv):
+        """``conv`` as a modulated convolution: demodulated in front of a LeakyReLU, modulated only where tanh follows (StyleGAN2's
+        toRGB); under ``equalized_lr`` around the EqualizedLearningRate the stack would have put there."""
+        tanh = conv.activation == "tanh"
+        if self.equalized_lr:
+            conv = layers.EqualizedLearningRate(conv, gain=1.0 if tanh else math.sqrt(2))
+        return layers.StyleModulation(conv, demodulate=not tanh)
 
 
 class DCGANDiscriminator(layers.SpectralSequential):

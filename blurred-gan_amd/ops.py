@@ -484,6 +484,74 @@ class noise:
         return dstrength
 
 
+# ------------------------------------------------------------------ style modulation (include/bgan.h "style modulation")
+class modconv:
+    """The StyleModulation kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's
+    public functions by name; these calls are recorded by the modconv tests' own recorder."""
+
+    @staticmethod
+    def dot_plan(B, P, Cc, aligned=True):
+        """How ``dot`` cuts a [B, P, Cc] call: float4 or single-float units, channel lanes per workgroup, chunks of the channel axis
+        and slabs of pixels (more than one: the two-launch route with scratch)."""
+        v = (C.c_int * _lib.MOD_DOT_PLAN_INTS)()
+        check(_lib.load().bg_mod_dot_plan(int(B), int(P), int(Cc), v), "bg_mod_dot_plan")
+        vec, lanes, chunks, slabs = v[0:4] if aligned else v[4:8]
+        return dict(vec=vec, lanes=lanes, chunks=chunks, slabs=slabs)
+
+    @staticmethod
+    def dot_workspace_bytes(B, P, Cc):
+        return int(_lib.load().bg_mod_dot_workspace_bytes(B, P, Cc))
+
+    @staticmethod
+    def scale(x, v, out, B, P, Cc, bias=None, lrelu_alpha=1.0):
+        """out[n, p, c] = LeakyReLU(x[n, p, c] * v[n, c] (+ bias[c])); out may be x."""
+        _f32(x, v, out, bias)
+        assert x.numel() == B * P * Cc == out.numel() and v.numel() == B * Cc and (bias is None or bias.numel() == Cc)
+        check(_lib.load().bg_mod_scale_f32(_ptr(x), _ptr(v), _ptr(bias), _ptr(out), B, P, Cc, lrelu_alpha, _stream()), "bg_mod_scale_f32")
+        return out
+
+    @staticmethod
+    def dot(a, b, out, B, P, Cc, ws=None, beta=0.0, scale=1.0):
+        """out[n, c] = beta * out + scale * sum_p a[n, p, c] * b[n, p, c]: a fixed order, the same bits every run."""
+        _f32(a, b, out)
+        assert a.numel() == B * P * Cc == b.numel() and out.numel() == B * Cc
+        nb = 0 if ws is None else ws.numel() * ws.element_size()
+        check(_lib.load().bg_mod_dot_f32(_ptr(a), _ptr(b), _ptr(out), B, P, Cc, _ptr(ws), nb, beta, scale, _stream()), "bg_mod_dot_f32")
+        return out
+
+    @staticmethod
+    def wsq(w, q, taps, I, O, transposed=False):
+        """q[i, o] = sum over the taps of w^2; w is [taps, I, O], or [taps, O, I] with ``transposed`` (a Conv2DTranspose kernel)."""
+        _f32(w, q)
+        assert w.numel() == taps * I * O and q.numel() == I * O
+        check(_lib.load().bg_mod_wsq_f32(_ptr(w), _ptr(q), taps, I, O, int(transposed), _stream()), "bg_mod_wsq_f32")
+        return q
+
+    @staticmethod
+    def wsq_grad(w, dq, dw, taps, I, O, transposed=False, scale=1.0):
+        """dw += scale * 2 * w * dq, dq [I, O] broadcast over the taps of either kernel layout."""
+        _f32(w, dq, dw)
+        assert w.numel() == taps * I * O == dw.numel() and dq.numel() == I * O
+        check(_lib.load().bg_mod_wsq_grad_f32(_ptr(w), _ptr(dq), _ptr(dw), taps, I, O, int(transposed), scale, _stream()), "bg_mod_wsq_grad_f32")
+        return dw
+
+    @staticmethod
+    def demod(s, q, d, B, I, O, eps=1e-8):
+        """d[n, o] = 1 / sqrt(sum_i s[n, i]^2 * q[i, o] + eps)."""
+        _f32(s, q, d)
+        assert s.numel() == B * I and q.numel() == I * O and d.numel() == B * O
+        check(_lib.load().bg_mod_demod_f32(_ptr(s), _ptr(q), _ptr(d), B, I, O, eps, _stream()), "bg_mod_demod_f32")
+        return d
+
+    @staticmethod
+    def demod_bwd(d, dd, s, q, dq, ds, B, I, O):
+        """dq = -1/2 * d^3 * dd; ds[n, i] += 2 * s[n, i] * sum_o dq[n, o] * q[i, o]."""
+        _f32(d, dd, s, q, dq, ds)
+        assert d.numel() == dd.numel() == dq.numel() == B * O and s.numel() == ds.numel() == B * I and q.numel() == I * O
+        check(_lib.load().bg_mod_demod_bwd_f32(_ptr(d), _ptr(dd), _ptr(s), _ptr(q), _ptr(dq), _ptr(ds), B, I, O, _stream()), "bg_mod_demod_bwd_f32")
+        return dq, ds
+
+
 # ------------------------------------------------------------------ differentiable augmentation (include/bgan.h)
 class diffaug:
     """The DiffAugment kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's public

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, diffaugment, dist, ema as ema_mod, objective as objective_mod, ops, optimizers, program
 from .gaussian_blur import Variable
-from .layers import Sequential, get_seed
+from .layers import Sequential, StyleModulation, get_seed
 from .utils import JsonSerializable, ParseableFromCommandLine
 
 # the switches the engine / the library read per call that shape a step's launch list ("per call (step key)")
@@ -150,6 +150,10 @@ class WGAN:
         if any(l.kind == "noise" for l, _ in self.discriminator.flat_layers()):
             raise NotImplementedError("NoiseInjection in the discriminator: the layer is the generator's noise input; a critic with it "
                                       "has no gradient-penalty route (NoiseInjection in a critic under the gradient penalty is not built)")
+        if any(isinstance(l, StyleModulation) for l, _ in self.discriminator.flat_layers()):
+            raise NotImplementedError("StyleModulation in the discriminator: the layer is the generator's modulated convolution; a critic "
+                                      "with it has no gradient-penalty route (StyleModulation in a critic under the gradient penalty is not "
+                                      "built)")
         self.discriminator.optimizer = optimizers.Adam(self.hparams.learning_rate)
         self.d_steps_per_g_step = self.hparams.d_steps_per_g_step
         self.batch_size = None

@@ -132,15 +132,16 @@ def make_parser():
     parser.add_argument("--critic-mbstd", dest="critic_mbstd", type=int, default=0, metavar="G",
                         help="minibatch standard deviation layer in front of the critic's head, over groups of G consecutive samples "
                              "(0: off; the batch size must be a multiple of G)")
-    parser.add_argument("--generator-norm", dest="generator_norm", default="batch", choices=["batch", "pixel"],
+    parser.add_argument("--generator-norm", dest="generator_norm", default="batch", choices=["batch", "pixel", "style"],
                         help="generator normalisation: BatchNormalization in front of every LeakyReLU (default, the reference's) or a "
                              "PixelNormalization behind it (ProGAN / StyleGAN: per pixel, no variables, no batch statistics; the Dense "
-                             "and the hidden convolutions then carry a bias)")
+                             "and the hidden convolutions then carry a bias), or 'style': StyleGAN2's modulated convolutions with weight "
+                             "demodulation, the styles taken from the latents (no mapping network)")
     parser.add_argument("--normalize-latents", dest="normalize_latents", action="store_true",
                         help="a PixelNormalization of the latent vectors in front of the generator's Dense")
     parser.add_argument("--generator-noise", dest="generator_noise", action="store_true",
                         help="StyleGAN's per-pixel noise inputs: a NoiseInjection (strength * N(0, 1) per pixel, one learned strength per "
-                             "layer, initialised to zero) behind every hidden convolution of the generator (needs --generator-norm pixel)")
+                             "layer, initialised to zero) behind every hidden convolution of the generator (needs --generator-norm pixel or style)")
     parser.add_argument("--latent-distribution", dest="latent_distribution", default="uniform", choices=["uniform", "normal"],
                         help="the latents' distribution: uniform on [0, 1) (default, the reference's) or N(0, I) (the ProGAN / StyleGAN "
                              "papers'; what --normalize-latents is meant to normalise)")

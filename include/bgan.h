@@ -330,6 +330,35 @@ int bg_noise_add_f32(const float* x, const float* noise, const float* strength, 
 size_t bg_noise_grad_workspace_bytes(int R, int C);
 int bg_noise_grad_f32(const float* dz, const float* noise, float* dstrength, int R, int C, void* ws, float beta, float scale, void* stream);
 
+/* ---- style modulation (StyleGAN2, Karras et al. 2020; layers.StyleModulation), un-fused: the activations are scaled, fp32 --------
+ * One modulated stage: B samples of P pixels, I input and O output channels, styles s [B, I].  xs = x * s[n, :] goes through the
+ * ordinary convolution; with demodulation its output z is scaled by d[n, :] = 1 / sqrt((s * s) . Q + eps), Q[i, o] = sum over the
+ * taps of W^2 (it depends on the weights only).  Every sum runs in a fixed order, no atomics: two runs give the same bits; products
+ * and sums are rounded separately.  Pointers 4-byte aligned (BG_ERR_BAD_ALIGNMENT); float4 accesses where C % 4 == 0 and every
+ * matrix of the call is 16-byte aligned, single floats otherwise: no call is refused for a misaligned view.  Any size >= 1.  A
+ * refused call launches nothing.  No call takes a step-program binding: every operand is device memory.
+ *   scale      out[n, p, c] = act(in[n, p, c] * v[n, c] (+ bias[c])), act = LeakyReLU(lrelu_alpha) (1: none); bias may be NULL; out
+ *              may alias in.  Serves xs, y = d * z + bias, dz = d * dy and dx = s * dxs.
+ *   dot        out[n, c] = beta * out + scale * sum_p a[n, p, c] * b[n, p, c] (beta = 0: out is not read).  Serves dd = sum dy * z
+ *              and ds = sum x * dxs.  Large P with few channels is cut into slabs of pixels whose sums a second launch adds in slab
+ *              order: ws of bg_mod_dot_workspace_bytes(B, P, C) bytes (0: none needed; ws may then be NULL).  bg_mod_dot_plan (host
+ *              only): {vec, lanes, chunks, slabs} with float4 units allowed, then the four with single floats.
+ *   wsq        Q [I, O] from a kernel [taps, I, O] (Conv2D) or, transposed != 0, [taps, O, I] (Conv2DTranspose); taps in index order.
+ *   demod      d[n, o] = 1 / sqrt(sum_i (s[n, i] * s[n, i]) * Q[i, o] + eps), i in index order; correctly rounded sqrt and division.
+ *   demod_bwd  dq[n, o] = -1/2 * d^3 * dd[n, o];  ds[n, i] += 2 * s[n, i] * sum_o dq[n, o] * Q[i, o]   (two launches).
+ *   wsq_grad   dw[t, ., .] += scale * 2 * w[t, ., .] * dQ (dQ [I, O], broadcast over the taps, either kernel layout). */
+#define BG_MOD_DOT_PLAN_INTS 8
+int bg_mod_scale_f32(const float* in, const float* v, const float* bias, float* out, int B, int P, int C, float lrelu_alpha, void* stream);
+int bg_mod_dot_plan(int B, int P, int C, int* out);
+size_t bg_mod_dot_workspace_bytes(int B, int P, int C);
+int bg_mod_dot_f32(const float* a, const float* b, float* out, int B, int P, int C, void* ws, size_t ws_bytes, float beta, float scale,
+                   void* stream);
+int bg_mod_wsq_f32(const float* w, float* q, int taps, int I, int O, int transposed, void* stream);
+int bg_mod_wsq_grad_f32(const float* w, const float* dq, float* dw, int taps, int I, int O, int transposed, float scale, void* stream);
+int bg_mod_demod_f32(const float* s, const float* Q, float* d, int B, int I, int O, float eps, void* stream);
+int bg_mod_demod_bwd_f32(const float* d, const float* dd, const float* s, const float* Q, float* dq, float* ds, int B, int I, int O,
+                         void* stream);
+
 /* ---- differentiable augmentation (DiffAugment, Zhao et al. 2020) of the critic's input, NHWC fp32 -----------------------------
  * Per sample an affine map T(x) = L x + k of its [H, W, C] map: colour, then translation, then cutout.  ops_mask: bit 0 colour,
  * bit 1 translation, bit 2 cutout; an absent operation takes its neutral value and does no arithmetic (without colour values are
