@@ -94,6 +94,11 @@ SIGNATURES = {
     "bg_mod_wsq_grad_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "bg_mod_demod_f32": (_i, [_p, _p, _p, _i, _i, _i, _f, _p]),
     "bg_mod_demod_bwd_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "bg_dense_lrelu_plan": (_i, [_i, _i, _i, C.POINTER(_i)]),
+    "bg_dense_lrelu_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p]),
+    "bg_lrelu_bias_bwd_workspace_bytes": (_z, [_i, _i]),
+    "bg_lrelu_bias_bwd_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _f, _f, _p, _z, _p]),
+    "bg_truncate_f32": (_i, [_p, _p, _p, _f, _i, _i, _p]),
     "bg_diffaug_route": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "bg_diffaug_plan": (_i, [_i, _i, _i, _i, _i] + [C.POINTER(_i)] * 5),
     "bg_diffaug_decode": (_i, [C.POINTER(_f), _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_i)]),
@@ -181,6 +186,7 @@ COMM_ID_BYTES = 128
 PIXELNORM_ROUTE_INTS = 8       # include/bgan.h BG_PIXELNORM_ROUTE_INTS
 NOISE_ROUTE_INTS = 8           # include/bgan.h BG_NOISE_ROUTE_INTS
 MOD_DOT_PLAN_INTS = 8          # include/bgan.h BG_MOD_DOT_PLAN_INTS
+DENSE_LRELU_PLAN_INTS = 4      # include/bgan.h BG_DENSE_LRELU_PLAN_INTS
 MBSTD_PLAN_INTS = 12          # include/bgan.h BG_MBSTD_PLAN_INTS
 SPECTRAL_DESC_INTS = 16        # include/bgan.h BG_SPECTRAL_DESC_INTS
 EQLR_DESC_INTS = 12            # include/bgan.h BG_EQLR_DESC_INTS

@@ -135,9 +135,12 @@ class AdaptiveBlurController(Callback):
 class GenerateSampleGridCallback(ExecuteEveryNExamplesCallback):
     """callbacks.py:209-236: an 8x8 grid of samples from fixed latents, written as PNG (PIL, no matplotlib)."""
 
-    def __init__(self, log_dir: str, show_blurred_samples=True, every_n_examples=1000, also_save_files=True, use_ema=None):
-        """``use_ema``: sample from the averaged generator (``WGAN(generator_ema=...)``); None = when the model has one."""
+    def __init__(self, log_dir: str, show_blurred_samples=True, every_n_examples=1000, also_save_files=True, use_ema=None,
+                 truncation_psi=None):
+        """``use_ema``: sample from the averaged generator (``WGAN(generator_ema=...)``); None = when the model has one.
+        ``truncation_psi``: the truncation trick of a generator with a mapping network (``generate_samples(truncation_psi=...)``)."""
         self.log_dir = log_dir
+        self.truncation_psi = truncation_psi
         self.use_ema = use_ema
         self.show_blurred_samples = show_blurred_samples
         super().__init__(n=every_n_examples)
@@ -156,7 +159,8 @@ class GenerateSampleGridCallback(ExecuteEveryNExamplesCallback):
         use_ema = self.use_ema
         if use_ema is None:
             use_ema = getattr(self.model, "generator_ema", None) is not None
-        samples = self.model.generate_samples(self.latents, training=False, **({"ema": True} if use_ema else {}))
+        kw = {} if self.truncation_psi is None else {"truncation_psi": self.truncation_psi}
+        samples = self.model.generate_samples(self.latents, training=False, **({"ema": True} if use_ema else {}), **kw)
         if self.show_blurred_samples and hasattr(self.model, "blur"):
             samples = self.model.blur(samples)
         s = normalize_images(samples).clamp(0, 1).cpu().numpy()

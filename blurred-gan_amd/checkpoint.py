@@ -44,6 +44,14 @@ def _eqlr_signature(model):
     return [float(np.float32(l.coefficient)) for l in model.net().eqlr_layers]
 
 
+def _mapping_signature(model):
+    """The configuration of the model's MappingNetwork prefix as a JSON string ("null": none): the layer count and width behind its
+    variables, and the multiplier and switch that decide what its raw kernels mean."""
+    mp = model.net().mapping
+    return json.dumps(None if mp is None else dict(num_layers=mp.num_layers, units=model.net().style_dim, lr_multiplier=mp.lr_multiplier,
+                                                    equalized_lr=mp.equalized_lr), sort_keys=True)
+
+
 class CheckpointManager:
     def __init__(self, gan, directory, max_to_keep=5, keep_checkpoint_every_n_hours=None):
         self.gan, self.directory = gan, directory
@@ -106,6 +114,7 @@ class CheckpointManager:
             d[f"{tag}_opt_lr"] = np.float64(lr if not callable(lr) else np.nan)      # a schedule lives in the config
             d[f"{tag}_rng_offset"] = np.int64(int(model.net().rng_offset))        # dropout-mask stream of this network
             d[f"{tag}_eqlr"] = np.asarray(_eqlr_signature(model), dtype=np.float32)
+            d[f"{tag}_mapping"] = np.str_(_mapping_signature(model))
         if getattr(g, "generator_ema", None) is not None:
             st = g.generator_ema.store
             d["g_ema_theta"] = st.theta.cpu().numpy()
@@ -152,6 +161,11 @@ class CheckpointManager:
                 raise ValueError(f"{path}: the {'generator' if tag == 'g' else 'discriminator'} was saved with the equalised-learning-rate "
                                  f"coefficients {saved_eqlr}, the model's wrapped layers have {_eqlr_signature(model)}: the raw kernels of "
                                  "one are not the weights of the other (an empty list is a plain model)")
+            saved_map = str(d[f"{tag}_mapping"]) if f"{tag}_mapping" in d.files else "null"      # older files: no mapping network
+            if json.loads(saved_map) != json.loads(_mapping_signature(model)):
+                raise ValueError(f"{path}: the {'generator' if tag == 'g' else 'discriminator'} was saved with the mapping network "
+                                 f"{saved_map}, the model's is {_mapping_signature(model)}: layer count, width, lr_multiplier and "
+                                 "equalized_lr must match (the raw kernels of one are not the weights of the other)")
         ada = getattr(g, "_ada_state", None) is not None
         if ada and "aug_config" in d.files and json.loads(str(d["aug_config"])) != g.augment.get_config():
             raise ValueError(f"{path}: saved with the adaptive augmentation {json.loads(str(d['aug_config']))}, the model's is "

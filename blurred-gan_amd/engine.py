@@ -17,6 +17,8 @@ own too (csrc/mbstd.hip; one launch each way, one more for the penalty's tangent
                                              that is the network's first layer normalises the latents, one launch, no backward
   NoiseInjection + LeakyReLU              -> one in-place pass over the conv's stored output (csrc/noise.hip), in front of the
                                              PixelNormalization pass where the stage has one; all noise maps of a pass are one draw
+  MappingNetwork (not a stage)            -> one launch per layer in front of the first stage: Dense + bias + LeakyReLU in the
+                                             epilogue (csrc/mapping.hip); its output is the first Dense's input and the style source
 
 Net.forward and Net.backward are input / pass set-up, a loop over the stages, and one helper per concern (DESIGN.md §5
 "Engine map"); tests/test_engine_trace_cpu.py holds the order and the arguments of everything they enqueue.
@@ -32,7 +34,7 @@ import torch
 
 from . import dist, ops
 from ._lib import EPI_NONE, EPI_BIAS_LRELU, EPI_MUL_GRAD, EPI_TANH, EPI_AFFINE_LRELU
-from .layers import MOD_RULE, EqualizedLearningRate, SpectralNormalization, StyleModulation
+from .layers import MAPPING_RULE, MOD_RULE, EqualizedLearningRate, SpectralNormalization, StyleModulation
 
 
 RESAMPLE = ("upsample", "avgpool", "firup", "firdown")      # "fir*": the FIR-filtered pair (layers.Filtered*Sampling2D)
@@ -178,6 +180,14 @@ class Context(_StageBuffers):
             if st.mod is not None:
                 self.mod_s[i], self.mod_xs[i] = f(B, st.in_shape[-1]), f(B, *st.in_shape)
                 self.mod_d[i] = f(B, st.out_shape[-1]) if st.mod.demodulate else None
+        # MappingNetwork prefix: its input of the pass (z, or the normalised latents), the layers' outputs h_1 .. h_n (h_n = w), dL/dw
+        # as the backward collects it, a second [B, U] buffer the mapping backward alternates with, the truncated w and the batch
+        # mean of w that the running average takes
+        self.map_in, self.map_h, self.mod_dw, self.map_g, self.map_trunc, self.map_mean = None, [], None, None, None, None
+        if net.has_mapping:
+            U = net.style_dim
+            self.map_h = [f(B, U) for _ in range(net.mapping.num_layers)]
+            self.mod_dw, self.map_g = f(B, U), f(B, U)
         self._net, self._device = net, device
         net.check_rows(B)
         self._extra = {}
@@ -312,6 +322,7 @@ class _BackwardPass:
     """What one Net.backward call carries from stage to stage."""
 
     def __init__(self, ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, sync_bn, keep_u_rows=None):
+        self.dw_started = False         # a mapping prefix: dL/dw has its first contribution of the pass (the next ones add)
         self.ctx, self.need_dw, self.beta, self.scale, self.reducer = ctx, need_dw, beta, scale, reducer
         self.keep_u_rows = keep_u_rows      # LN stages keep u of these samples for the penalty's second order
         self.dw_rows = ctx.B if dw_rows is None else int(dw_rows)
@@ -338,7 +349,9 @@ class Net:
         self.capture_branches = None     # test instrumentation (gp_second_order_merged): a list collects the x-hat rows' LeakyReLU signs
         self.stages: List[Stage] = []
         self.latent_pn = None            # layers.PixelNormalization as the network's first layer: the latents' normalisation
+        self.mapping = None              # layers.MappingNetwork in front of the first stage: z -> w, the style source
         self.in_shape = tuple(flat_layers[0][1])
+        self.style_dim = self.in_shape[0] if len(self.in_shape) == 1 else None      # the size of the style source: L, or the prefix's units
         cur = None
         n_masks = 0
         for idx, (l, s) in enumerate(flat_layers):
@@ -357,6 +370,8 @@ class Net:
                 if cur.mod is not None: self.mod_place(flat_layers, idx, cur)      # noqa: E701
             elif k in ("bn", "layernorm", "dropout", "pixelnorm") and cur is not None and cur.mod is not None:
                 raise NotImplementedError(MOD_RULE + f" (a {type(l).__name__} in the stage of a StyleModulation)")
+            elif k == "mapping":
+                self.mapping_place(flat_layers, idx, cur)
             elif k == "pixelnorm":
                 self.pn_place(flat_layers, idx, cur)
             elif k in ("bn", "layernorm", "dropout", "lrelu") and cur is not None and cur.pn is not None:
@@ -433,6 +448,7 @@ class Net:
         self.noise_pixels = sum(st.noise_pixels for st in self.stages if st.noise is not None)     # P: noise values per sample
         self.mod_layers = [st.lin for st in self.stages if st.mod is not None]
         self.has_mod = bool(self.mod_layers)
+        self.has_mapping = self.mapping is not None
         self._ctx = {}
         self._rows_checked = set()
         self._ws = None
@@ -584,7 +600,8 @@ class Net:
             return ops.blur_nhwc(x, y, taps, nt, tmp)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, ctx: Context, inputs, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None, augment=None, noise=None):
+    def forward(self, ctx: Context, inputs=None, training=False, masks=None, seed=0, lerp_alpha=None, lerp_out=None, augment=None, noise=None,
+                w=None, truncation_psi=None):
         """inputs: a tensor [B,...] or a list of tensors concatenated along the batch.  ``training`` switches
         Dropout and BatchNormalization exactly as Keras' ``training=`` argument does.
         ``lerp_alpha`` (with inputs = [f, r]): a third batch slice x-hat = r + alpha (f - r) follows the two (wgan.py:239).  Behind
@@ -592,16 +609,21 @@ class Net:
         fly (bg_blur3_lerp_nhwc_f32); otherwise x-hat is written to ``lerp_out`` by bg_lerp_f32 and joins the list.
         ``augment`` = (DiffAugment, params [B, 8]): the assembled (blurred) batch goes through T into a second input-sized buffer,
         which is what stage 0 reads; the pass's backward applies L^T ahead of blur^T (aug_forward / aug_backward).
+        ``w`` (a network with a MappingNetwork prefix, in place of ``inputs``): [B, units] styles; the prefix is skipped.
+        ``truncation_psi`` (such a network, inference only): w <- w_avg + psi * (w - w_avg) between prefix and synthesis network.
         ``noise`` (a network with NoiseInjection stages; in training and in inference alike): None draws the maps of all stages
         with ONE launch from ``seed`` and this network's counter, as the one-draw keep mask is drawn; a tensor [B, P] (per sample,
         the stages' maps in network order) is copied in; False leaves the noise launches out, as if every strength were 0."""
         if self.store.tr_dirty:
             self.prepare_weights()
-        x = self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)
+        if w is not None or truncation_psi is not None: self.mapping_check_call(ctx, inputs, w, truncation_psi, training)      # noqa: E701
         ctx.aug = augment
+        x = w if w is not None else self._assemble_input(ctx, inputs, lerp_alpha, lerp_out)      # w: the styles stand in for the prefix's output
         if augment is not None: x = self.aug_forward(ctx, x)      # noqa: E701
-        if self.latent_pn is not None: x = self.pn_latents(ctx, x)      # noqa: E701
-        if self.has_mod: ctx.mod_w = x.view(ctx.B, *self.in_shape)      # noqa: E701  (the style source of every modulated stage)
+        if self.latent_pn is not None and w is None: x = self.pn_latents(ctx, x)      # noqa: E701
+        if self.has_mapping and w is None: x = self.mapping_forward(ctx, x)      # noqa: E701
+        if truncation_psi is not None: x = self.mapping_truncate(ctx, x, truncation_psi)      # noqa: E701
+        if self.has_mod or self.has_mapping: ctx.mod_w = x.view(ctx.B, self.style_dim)      # noqa: E701  (the style source of every modulated stage)
         ctx.dropout_active = bool(training)
         # one launch draws the masks of all stages; where their rates differ, or masks are handed in, each stage sets its own
         one_draw = bool(training and masks is None and ctx.keep_rate is not None and ctx.keep_total)
@@ -791,7 +813,7 @@ class Net:
         and Dense gradients are still taken here).  ``keep_u_rows`` = (lo, hi): LayerNormalization stages keep u, the gradient at
         their normalised pre-activation, for those samples (the x-hat rows: gp_second_order's source term needs it)."""
         if need_dx and self.latent_pn is not None: raise NotImplementedError("the gradient at the input of a network that starts with a PixelNormalization (the latents' normalisation has no backward)")  # noqa: E701
-        if need_dx and self.has_mod: raise NotImplementedError("the gradient at the input of a network with StyleModulation stages (dL/dw, the gradient through the styles, is not built)")  # noqa: E701
+        if need_dx and self.has_mod and not self.has_mapping: raise NotImplementedError("the gradient at the input of a network with StyleModulation stages (dL/dw, the gradient through the styles, is not built)")  # noqa: E701
         if need_dw:
             self.store.ensure_opt_state()
         p = _BackwardPass(ctx, need_dw, beta, scale, reducer, dw_rows, defer_conv_dw, self.sync_bn and dist.collectives_active(),
@@ -811,6 +833,7 @@ class Net:
             overlap = has_dw and p.sync_bn and prev is not None and prev.bn is not None
             if has_dw and not overlap:
                 self._weight_grads(p, i, st, dz)
+            if i == 0 and self.has_mapping and (need_dw or need_dx): return self.mapping_backward(p, st, dz, need_dx)      # noqa: E701
             if i == 0 and not need_dx:
                 p.release_deferred()
                 return None
@@ -1075,7 +1098,7 @@ class Net:
         """Net.__init__'s placement rule for the StyleModulation at ``flat_layers[idx]``, the linear layer of the new stage ``cur``:
         the network's input is the [L] style vector and another stage stands in front; everything else is refused.  (What may
         follow in the stage is checked as the layers arrive; what the wrapper may wrap, by the wrapper.)"""
-        if len(self.in_shape) != 1 or len(self.stages) < 2 or cur.mod.style_dim != self.in_shape[0]:
+        if len(self.in_shape) != 1 or len(self.stages) < 2 or cur.mod.style_dim != self.style_dim:
             raise NotImplementedError(MOD_RULE + " (a first stage has no style source: the only one is the network's [L] input)")
 
     def mod_geom(self, st):
@@ -1097,7 +1120,7 @@ class Net:
         B, v = ctx.B, st.lin.vars
         (Pi, Po), I, O = st.mod_pixels, st.in_shape[-1], st.out_shape[-1]
         s, xs = ctx.mod_s[i], ctx.mod_xs[i]
-        ops.gemm(ctx.mod_w, v["style_kernel"], s, B, I, self.in_shape[0], bias=v["style_bias"])
+        ops.gemm(ctx.mod_w, v["style_kernel"], s, B, I, self.style_dim, bias=v["style_bias"])
         ops.modconv.scale(xin, s, xs, B, Pi, I)
         if not st.mod.demodulate:
             self._conv(st, xs, out, False, EPI_TANH if st.act == "tanh" else EPI_NONE)
@@ -1116,7 +1139,7 @@ class Net:
         the stage below applies its own activation backward (ds needs the unmasked dxs, so nothing is fused into the data
         gradient).  The stage's slice goes to the reducer at the end: its last writer is here."""
         ctx, v = p.ctx, st.lin.vars
-        B, L = ctx.B, self.in_shape[0]
+        B, L = ctx.B, self.style_dim
         if p.dw_rows != B: raise NotImplementedError("weight gradients from a part of the batch through a StyleModulation stage")      # noqa: E701
         (Pi, Po), I, O = st.mod_pixels, st.in_shape[-1], st.out_shape[-1]
         s, xs, xin, demod = ctx.mod_s[i], ctx.mod_xs[i], ctx.xin[i], st.mod.demodulate
@@ -1147,6 +1170,9 @@ class Net:
                 ops.modconv.wsq_grad(self.store.kernel(st.lin), dQ, g(st.lin, "kernel"), taps, I, O, transposed=tr, scale=p.scale)
             ops.gemm(ctx.mod_w, ds, g(st.lin, "style_kernel"), L, I, B, transA=True, beta=p.beta, scale=p.scale)
             ops.colsum(ds, g(st.lin, "style_bias"), B, I, self.workspace(ops.colsum_workspace_bytes(B, I)), beta=p.beta, scale=p.scale)
+            if self.has_mapping:        # this stage's share of dL/dw = ds . style_kernel^T; the first contributor of the pass overwrites
+                ops.gemm(ds, v["style_kernel"], ctx.mod_dw, B, L, I, transB=True, beta=1.0 if p.dw_started else 0.0)
+                p.dw_started = True
             if p.reducer is not None:
                 p.reducer.ready(*self._train_range(st))
         ops.modconv.scale(tgt, s, tgt, B, Pi, I)
@@ -1155,6 +1181,90 @@ class Net:
     def mod_dot_ws(self, B, P, Cc):
         nb = ops.modconv.dot_workspace_bytes(B, P, Cc)
         return self.workspace(nb) if nb else None
+
+    # ---- MappingNetwork (DESIGN.md §5 "Mapping network").  Public names for the reason the LayerNormalization helpers carry them: no
+    # configuration of the engine-trace fixture has the layer; tests/test_mapping_cpu.py holds the placement rules and the formulas,
+    # tests/test_mapping_step_gpu.py what these compute.
+    MAPPING_RULE = MAPPING_RULE
+
+    def mapping_place(self, flat_layers, idx, cur):
+        """Net.__init__'s placement rule for the MappingNetwork at ``flat_layers[idx]``: in front of the first stage, first in the
+        network or directly behind the latents' PixelNormalization, once; everything else is refused."""
+        l, s = flat_layers[idx]
+        ok = (self.mapping is None and cur is None and self.blur is None and len(self.in_shape) == 1 and len(s) == 1
+              and (idx == 0 or (idx == 1 and self.latent_pn is not None)))
+        if not ok:
+            raise NotImplementedError(MAPPING_RULE)
+        self.mapping, self.style_dim = l, int(l.units_for(s))
+
+    def mapping_check_call(self, ctx, inputs, w, truncation_psi, training):
+        """The arguments of a forward that names ``w`` or ``truncation_psi``."""
+        if not self.has_mapping:
+            raise ValueError("forward(w=..., truncation_psi=...): this network has no MappingNetwork prefix")
+        if w is not None and inputs is not None:
+            raise ValueError("forward: either inputs (the latents z) or w (the styles, which skip the mapping network), not both")
+        if w is not None and tuple(w.shape) != (ctx.B, self.style_dim):
+            raise ValueError(f"forward: w must be [{ctx.B}, {self.style_dim}], got {tuple(w.shape)}")
+        if truncation_psi is not None and training:
+            raise ValueError("forward: truncation_psi is an inference-time trick; with training=True the backward would not see it")
+
+    def mapping_forward(self, ctx, x):
+        """w = the prefix on ``x`` (z, or the normalised latents): one launch per layer, every layer's output kept in ctx.map_h for
+        the backward.  The same in training and in inference."""
+        mp, B, U = self.mapping, ctx.B, self.style_dim
+        x = ctx.map_in = x.view(B, self.in_shape[0])
+        for l in range(mp.num_layers):
+            K = self.in_shape[0] if l == 0 else U
+            x = ops.mapping.dense_lrelu(x, mp.vars[f"kernel_{l}"], mp.vars[f"bias_{l}"], ctx.map_h[l], B, U, K, c=mp.coefficients[l],
+                                        bias_mul=mp.bias_multiplier, alpha=mp.alpha)
+        return x
+
+    def mapping_truncate(self, ctx, w, psi):
+        """The truncation trick on the pass's styles, into a buffer of the pass's own (the prefix's output stays as it is)."""
+        if ctx.map_trunc is None:
+            ctx.map_trunc = torch.empty((ctx.B, self.style_dim), dtype=torch.float32, device=self.device)
+        return ops.mapping.truncate(w.view(ctx.B, self.style_dim), self.mapping.vars["w_avg"], ctx.map_trunc, float(psi), ctx.B, self.style_dim)
+
+    def mapping_backward(self, p, st, dz, need_dx):
+        """The end of a backward through a network with a mapping prefix, at its first stage (a Dense on w) with ``dz`` the gradient
+        at that Dense's output: the Dense's data gradient is the LAST contribution to dL/dw in ctx.mod_dw, behind the modulated
+        stages' (mod_backward); then the prefix from top to bottom: LeakyReLU' and the bias sums in one pass, the kernel gradient,
+        the data gradient into the other [B, U] buffer (the bottom layer's into the pass's input gradient, only when ``need_dx``
+        asks for dL/dz).  The prefix's slice goes to the reducer last.  Returns dL/dz or None."""
+        ctx, mp = p.ctx, self.mapping
+        B, U, L = ctx.B, self.style_dim, self.in_shape[0]
+        if p.dw_rows != B: raise NotImplementedError("weight gradients from a part of the batch through a MappingNetwork")      # noqa: E701
+        if not p.need_dw: raise NotImplementedError("the gradient at the input of a network with a MappingNetwork without its weight gradients (need_dw=False)")  # noqa: E701
+        ops.gemm(dz.view(B, st.out_shape[0]), self.store.kernel(st.lin), ctx.mod_dw, B, U, st.out_shape[0], transB=True,
+                 beta=1.0 if p.dw_started else 0.0)
+        p.dw_started = True
+        g, other = ctx.mod_dw, ctx.map_g
+        grad = self.store.grad_of
+        ws = self.workspace(ops.mapping.workspace_bytes(B, U))
+        for l in range(mp.num_layers - 1, -1, -1):
+            hin, K, c = (ctx.map_in, L, mp.coefficients[l]) if l == 0 else (ctx.map_h[l - 1], U, mp.coefficients[l])
+            ops.mapping.lrelu_bias_bwd(g, ctx.map_h[l], g, grad(mp, f"bias_{l}"), B, U, ws, alpha=mp.alpha, beta=p.beta,
+                                       scale=p.scale * mp.bias_multiplier)
+            ops.gemm(hin, g, grad(mp, f"kernel_{l}"), K, U, B, transA=True, beta=p.beta, scale=p.scale * c)
+            if l > 0 or need_dx:
+                tgt = other if l > 0 else ctx.input_grad()
+                ops.gemm(g, mp.vars[f"kernel_{l}"], tgt, B, K, U, transB=True, scale=c)
+                g, other = tgt, g
+        if p.reducer is not None:
+            p.reducer.ready(*self.store.train_range(mp))
+        p.release_deferred()
+        return g if need_dx else None
+
+    def w_avg_update(self, ctx, global_batch):
+        """w_avg <- w_avg - (1 - beta) * (w_avg - mean of the pass's w over the GLOBAL batch): the column sums of this rank's w scaled
+        by 1 / global batch, their sum over the ranks (one process: no collective), the running average: three launches, recorded
+        in a step program like any other."""
+        mp, B, U = self.mapping, ctx.B, self.style_dim
+        if ctx.map_mean is None:
+            ctx.map_mean = torch.empty(U, dtype=torch.float32, device=self.device)
+        ops.colsum(ctx.map_h[-1], ctx.map_mean, B, U, self.workspace(ops.colsum_workspace_bytes(B, U)), scale=1.0 / float(global_batch))
+        dist.all_reduce_sum_async(ctx.map_mean).wait()
+        ops.ema(mp.vars["w_avg"], ctx.map_mean, None, None, 1.0 - mp.w_avg_beta)
 
     # ---- DiffAugment in front of stage 0 (DESIGN.md §5 "Augmentation").  Public names for the reason the LayerNormalization helpers
     # carry them: the engine-trace fixture's configurations run without augmentation; tests/test_diffaug_cpu.py records these.

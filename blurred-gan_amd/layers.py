@@ -335,7 +335,8 @@ class StyleModulation(Layer):
     The un-fused form of the paper: the activations are scaled, not the weights.  In a Sequential the wrapper stands for its layer,
     as EqualizedLearningRate does: same kind, shapes, ``kernel`` and ``bias``; it adds the trainables ``style_kernel`` [L, I] (Glorot
     uniform) and ``style_bias`` [I] (ones).  L is the model's input size, known once the wrapper is part of a model with an input
-    shape.  No mapping network, no gradient with respect to w (DESIGN.md section 5 "Style modulation")."""
+    shape, or the ``units`` of the ``MappingNetwork`` the model starts with: then w is that layer's output and the gradient with
+    respect to w runs back into it (DESIGN.md section 5 "Style modulation", "Mapping network")."""
 
     def __init__(self, layer, demodulate=True, epsilon=1e-8, **kw):
         inner = layer.layer if isinstance(layer, EqualizedLearningRate) else layer
@@ -371,6 +372,76 @@ class StyleModulation(Layer):
         specs = list(self.layer.var_specs(in_shape))
         L, I = int(self.style_dim), int(in_shape[-1])
         return specs + [("style_kernel", (L, I), True, _glorot((L, I), L, I)), ("style_bias", (I,), True, _ones((I,)))]
+
+
+MAPPING_RULE = ("MappingNetwork is supported as the first layer of a generator whose input is an [L] vector, or directly behind the leading "
+                "PixelNormalization of normalize_latents=True, once per model: not in a critic, not behind a stage, not twice")
+
+
+class MappingNetwork(Layer):
+    """StyleGAN's mapping network ``G_mapping`` (Karras et al. 2019): ``num_layers`` Dense layers z [L] -> w [units] (``units=None``: L),
+    h_{l+1} = LeakyReLU_alpha(c_l * (h_l . kernel_l) + m * bias_l), the activation behind every layer, the last one included.  One
+    layer object: ``kernel_0 .. kernel_{n-1}`` ([L, U], then [U, U]), ``bias_0 .. bias_{n-1}`` ([U]) and the non-trainable running
+    mean ``w_avg`` [U] of the G-steps' w (zeros at the start; decay ``w_avg_beta``), which the truncation trick reads.  With
+    ``equalized_lr`` the kernels are drawn from N(0, 1) / lr_multiplier, c_l = sqrt(2) / sqrt(fan_in) * lr_multiplier and m =
+    lr_multiplier (StyleGAN's ``mapping_lrmul``: the optimizer sees a learning rate lr_multiplier times smaller); without, Glorot
+    uniform kernels and c_l = m = 1.  ``coefficients`` / ``bias_multiplier``: the fp32 values as Python floats, known once the input
+    shape is (as ``EqualizedLearningRate.coefficient``); they travel by value in the kernel arguments, not through the
+    effective-weight buffer.  The layer's output is the network's style source and the first Dense's input (DESIGN.md section 5
+    "Mapping network")."""
+    kind = "mapping"
+
+    def __init__(self, units=None, num_layers=8, lr_multiplier=0.01, alpha=0.2, equalized_lr=True, w_avg_beta=0.995, **kw):
+        super().__init__(**kw)
+        if isinstance(num_layers, bool) or int(num_layers) != num_layers or int(num_layers) < 1:
+            raise ValueError(f"MappingNetwork num_layers={num_layers!r}: at least one layer")
+        if units is not None and (isinstance(units, bool) or int(units) != units or int(units) < 1):
+            raise ValueError(f"MappingNetwork units={units!r}: None (the input size) or a positive size")
+        if isinstance(lr_multiplier, bool) or not isinstance(lr_multiplier, (int, float, np.integer, np.floating)) \
+                or not (math.isfinite(lr_multiplier) and lr_multiplier > 0):
+            raise ValueError(f"MappingNetwork lr_multiplier={lr_multiplier!r}: must be a positive finite number")
+        if not equalized_lr and float(lr_multiplier) != 1.0:
+            raise ValueError(f"MappingNetwork lr_multiplier={lr_multiplier!r} with equalized_lr=False: the multiplier is a run-time "
+                             "coefficient of the equalised learning rate; without it, it must be 1")
+        if not (math.isfinite(alpha) and alpha > 0.0):
+            raise ValueError(f"MappingNetwork alpha={alpha!r}: must be positive (the backward reads the branch off the stored output's sign)")
+        if not 0.0 <= float(w_avg_beta) < 1.0:
+            raise ValueError(f"MappingNetwork w_avg_beta={w_avg_beta!r}: a decay in [0, 1)")
+        self.units = None if units is None else int(units)
+        self.num_layers, self.lr_multiplier, self.alpha = int(num_layers), float(lr_multiplier), float(alpha)
+        self.equalized_lr, self.w_avg_beta = bool(equalized_lr), float(w_avg_beta)
+        self.coefficients = self.bias_multiplier = None
+
+    def units_for(self, in_shape):
+        if len(in_shape) != 1:
+            raise NotImplementedError(MAPPING_RULE + f" (on an input of shape {tuple(in_shape)})")
+        return int(in_shape[0]) if self.units is None else self.units
+
+    def out_shape(self, in_shape):
+        U = self.units_for(in_shape)
+        self._set_coefficients(int(in_shape[0]), U)
+        return (U,)
+
+    def _set_coefficients(self, L, U):
+        fans = [L] + [U] * (self.num_layers - 1)
+        if self.equalized_lr:        # in double, rounded to fp32 once
+            self.coefficients = [float(np.float32(math.sqrt(2.0) / math.sqrt(f) * self.lr_multiplier)) for f in fans]
+            self.bias_multiplier = float(np.float32(self.lr_multiplier))
+        else:
+            self.coefficients, self.bias_multiplier = [1.0] * self.num_layers, 1.0
+
+    def var_specs(self, in_shape):
+        U, L = self.units_for(in_shape), int(in_shape[0])
+        self._set_coefficients(L, U)
+        shapes = [(L, U)] + [(U, U)] * (self.num_layers - 1)
+        if self.equalized_lr:
+            inv = 1.0 / self.lr_multiplier
+            init = lambda sh: (lambda rng: (rng.standard_normal(sh) * inv).astype(np.float32))
+        else:
+            init = lambda sh: _glorot(sh, sh[0], sh[1])
+        specs = [(f"kernel_{l}", sh, True, init(sh)) for l, sh in enumerate(shapes)]
+        specs += [(f"bias_{l}", (U,), True, _zeros((U,))) for l in range(self.num_layers)]
+        return specs + [("w_avg", (U,), False, _zeros((U,)))]
 
 
 class LeakyReLU(Layer):
@@ -832,6 +903,10 @@ class Sequential(Layer):
         out, s = [], self._in_shape
         if s is None:
             raise RuntimeError("model has no input shape: give the first layer input_shape=")
+        style_dim = int(self._in_shape[0]) if len(self._in_shape) == 1 else None
+        head = self.layers[1:2] if self.layers and self.layers[0].kind == "pixelnorm" else self.layers[:1]
+        if style_dim is not None and head and isinstance(head[0], MappingNetwork):      # the style source is the mapping network's w
+            style_dim = head[0].units_for(self._in_shape)
         for l in self.layers:
             if isinstance(l, Sequential):
                 if l._in_shape is None:
@@ -839,8 +914,8 @@ class Sequential(Layer):
                 for ll, ss in l.flat_layers():
                     out.append((ll, ss))
             else:
-                if isinstance(l, StyleModulation):      # its style source is this model's input vector
-                    l.style_dim = int(self._in_shape[0]) if len(self._in_shape) == 1 else None
+                if isinstance(l, StyleModulation):      # its style source is this model's input vector, or the w of its mapping prefix
+                    l.style_dim = style_dim
                 out.append((l, tuple(s)))
             s = l.out_shape(s)
         return out

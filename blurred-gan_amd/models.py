@@ -41,8 +41,11 @@ StyleGAN's per-pixel noise inputs, one learned scalar ``noise_strength`` per lay
 ``normalization="style"`` (the generator) is StyleGAN2's: every hidden (transposed) convolution is a
 ``layers.StyleModulation(conv, demodulate=True)`` with bias, then the NoiseInjection of ``noise=True``, then LeakyReLU -- no
 PixelNormalization; the tanh output layer is ``StyleModulation(conv, demodulate=False)``.  The Dense block is the one ``"pixel"``
-builds.  The styles come from the model's own input vector (behind the PixelNormalization of ``normalize_latents=True``): there is no
-mapping network.  Every modulated layer gains ``style_kernel`` [L, I] and ``style_bias`` [I].  It combines with ``noise=True``,
+builds.  The styles come from the model's own input vector (behind the PixelNormalization of ``normalize_latents=True``), or, with
+``mapping_layers=N`` > 0, from StyleGAN's mapping network: a ``layers.MappingNetwork(units=mapping_units, num_layers=N,
+lr_multiplier=mapping_lr_multiplier)`` in front of the Dense (behind that PixelNormalization), whose output w [units] is both the
+Dense's input and every layer's style source; the stack's ``equalized_lr`` is passed on to it (without it the multiplier must be 1).
+``mapping_layers`` needs ``normalization="style"``.  Every modulated layer gains ``style_kernel`` [L, I] and ``style_bias`` [I].  It combines with ``noise=True``,
 ``equalized_lr=True``, every ``upsampling=`` and ``normalize_latents=True``; ``spectral_norm=True`` is refused.
 
 ``spectral_norm=True`` (either stack) wraps every Conv2D, Conv2DTranspose and Dense into ``layers.SpectralNormalization``: the
@@ -76,7 +79,8 @@ LATENT = {"mnist": 100, "celeba128": 100, "celeba64": 100, "tiny": 10, "tiny_mni
 
 class DCGANGenerator(layers.SpectralSequential):
     def __init__(self, latent_size=None, arch="celeba128", *args, upsampling="transpose", spectral_norm=False, normalization="batch",
-                 normalize_latents=False, equalized_lr=False, resample_kernel=(1, 3, 3, 1), noise=False, **kwargs):
+                 normalize_latents=False, equalized_lr=False, resample_kernel=(1, 3, 3, 1), noise=False, mapping_layers=0, mapping_units=None,
+                 mapping_lr_multiplier=0.01, **kwargs):
         super().__init__(*args, **kwargs)
         self.spectral_norm, self.equalized_lr = bool(spectral_norm), bool(equalized_lr)
         if self.spectral_norm and self.equalized_lr:
@@ -84,6 +88,12 @@ class DCGANGenerator(layers.SpectralSequential):
         if noise and normalization not in ("pixel", "style"):
             raise ValueError("noise=True needs normalization='pixel' or 'style': a NoiseInjection cannot stand in a BatchNormalization stage")
         self.noise = bool(noise)
+        if isinstance(mapping_layers, bool) or int(mapping_layers) != mapping_layers or int(mapping_layers) < 0:
+            raise ValueError(f"mapping_layers must be a layer count >= 0, got {mapping_layers!r}")
+        if mapping_layers and normalization != "style":
+            raise ValueError("mapping_layers > 0 needs normalization='style': the mapping network's output is the style source of the "
+                             "modulated convolutions")
+        self.mapping_layers, self.mapping_units, self.mapping_lr_multiplier = int(mapping_layers), mapping_units, mapping_lr_multiplier
         if upsampling not in ("transpose", "resize", "filtered"):
             raise ValueError(f"upsampling must be 'transpose', 'resize' or 'filtered', got {upsampling!r}")
         if normalization not in ("batch", "pixel", "style"):
@@ -100,6 +110,10 @@ class DCGANGenerator(layers.SpectralSequential):
         first = dict(input_shape=(self.latent_size,))
         if self.normalize_latents:
             self.add(layers.PixelNormalization(**first))
+            first = {}
+        if self.mapping_layers:
+            self.add(layers.MappingNetwork(units=mapping_units, num_layers=self.mapping_layers, lr_multiplier=mapping_lr_multiplier,
+                                           equalized_lr=self.equalized_lr, **first))
             first = {}
         self.add(layers.Dense(base * base * ch, use_bias=pixel, **first))
         if pixel:

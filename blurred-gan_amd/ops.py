@@ -484,6 +484,48 @@ class noise:
         return dstrength
 
 
+# ------------------------------------------------------------------ mapping network (include/bgan.h "mapping network")
+class mapping:
+    """The MappingNetwork kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's
+    public functions by name; these calls are recorded by the mapping tests' own recorder."""
+
+    @staticmethod
+    def plan(M, N, K):
+        """The tile of ``dense_lrelu`` and the workgroups of a call: dict(tile_m, tile_n, tile_k, workgroups)."""
+        v = (C.c_int * _lib.DENSE_LRELU_PLAN_INTS)()
+        check(_lib.load().bg_dense_lrelu_plan(int(M), int(N), int(K), v), "bg_dense_lrelu_plan")
+        return dict(tile_m=v[0], tile_n=v[1], tile_k=v[2], workgroups=v[3])
+
+    @staticmethod
+    def dense_lrelu(x, W, bias, y, M, N, K, c=1.0, bias_mul=1.0, alpha=1.0):
+        """y = LeakyReLU_alpha(c * (x . W) + bias_mul * bias); ``bias`` may be None; alpha = 1 is the linear case."""
+        _f32(x, W, bias, y)
+        assert x.numel() == M * K and W.numel() == K * N and y.numel() == M * N and (bias is None or bias.numel() == N)
+        check(_lib.load().bg_dense_lrelu_f32(_ptr(x), _ptr(W), _ptr(bias), _ptr(y), M, N, K, c, bias_mul, alpha, _stream()), "bg_dense_lrelu_f32")
+        return y
+
+    @staticmethod
+    def workspace_bytes(M, N):
+        return int(_lib.load().bg_lrelu_bias_bwd_workspace_bytes(M, N))
+
+    @staticmethod
+    def lrelu_bias_bwd(g, y, gp, dbias, M, N, ws, alpha=LRELU_ALPHA, beta=0.0, scale=1.0):
+        """gp = g * (y > 0 ? 1 : alpha) (gp may be g) and dbias = beta * old + scale * the column sums of gp, in a fixed order."""
+        _f32(g, y, gp, dbias)
+        assert g.numel() == M * N == y.numel() == gp.numel() and dbias.numel() == N
+        check(_lib.load().bg_lrelu_bias_bwd_f32(_ptr(g), _ptr(y), _ptr(gp), _ptr(dbias), M, N, alpha, beta, scale, _ptr(ws),
+                                                0 if ws is None else ws.numel() * ws.element_size(), _stream()), "bg_lrelu_bias_bwd_f32")
+        return gp
+
+    @staticmethod
+    def truncate(w, w_avg, out, psi, B, U):
+        """out = w_avg + psi * (w - w_avg) with the device-resident ``w_avg`` [U]; out may be w."""
+        _f32(w, w_avg, out)
+        assert w.numel() == B * U == out.numel() and w_avg.numel() == U
+        check(_lib.load().bg_truncate_f32(_ptr(w), _ptr(w_avg), _ptr(out), psi, B, U, _stream()), "bg_truncate_f32")
+        return out
+
+
 # ------------------------------------------------------------------ style modulation (include/bgan.h "style modulation")
 class modconv:
     """The StyleModulation kernels.  A namespace for the reason ``layernorm`` is one: the engine-trace maker knows the module's

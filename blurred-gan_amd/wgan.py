@@ -469,6 +469,9 @@ class WGAN:
                # the latents' draw is another kernel.  (A generator with NoiseInjection layers needs no field: the layers are fixed
                # at construction, a program belongs to one model, and n_train differs from the same stack without them)
                self.latent_distribution)
+        if G.has_mapping:
+            mp = G.mapping
+            key += (("mapping", mp.num_layers, G.style_dim, mp.lr_multiplier, mp.equalized_lr, mp.alpha, mp.w_avg_beta),)
         if self.generator_ema is not None:
             # the averaged model's presence, the two buffers the update writes and the schedule's static configuration: a program
             # recorded without the average, or on other buffers, never replays
@@ -547,22 +550,54 @@ class WGAN:
         assert self.batch_size is not None
         return self._latents("latents", (self.batch_size, self.latent_size))
 
-    def generate_samples(self, latents=None, training=False, ema=False, noise=None):
-        """``ema=True``: the averaged generator (``generator_ema=`` of the constructor), inference BatchNorm on its own averaged
+    @property
+    def w_avg(self):
+        """A host copy of the live generator's running mean of w (``layers.MappingNetwork``); None without a mapping network."""
+        mp = self.generator.net().mapping
+        return None if mp is None else mp.vars["w_avg"].detach().cpu().numpy().copy()
+
+    def map_latents(self, z, ema=False, truncation_psi=None):
+        """w = the mapping network of the (``ema``: averaged) generator on the latents ``z`` [B, L], behind the latents'
+        normalisation where the generator has one; ``truncation_psi``: pulled towards that generator's ``w_avg``.  A fresh [B, units]
+        tensor, what ``generate_samples(w=...)`` takes."""
+        if ema and self.generator_ema is None:
+            raise ValueError("map_latents(ema=True): this model has no averaged generator (construct it with generator_ema=...)")
+        G = (self.generator_ema if ema else self.generator).net()
+        if not G.has_mapping:
+            raise ValueError("map_latents: this generator has no MappingNetwork (DCGANGenerator(mapping_layers=N, normalization='style'))")
+        z = self._as_device(z)
+        ctx = G.context(int(z.shape[0]), "map")
+        if G.store.tr_dirty:
+            G.prepare_weights()
+        x = G.pn_latents(ctx, z) if G.latent_pn is not None else z
+        w = G.mapping_forward(ctx, x)
+        if truncation_psi is not None:
+            w = G.mapping_truncate(ctx, w, truncation_psi)
+        return w.clone()
+
+    def generate_samples(self, latents=None, training=False, ema=False, noise=None, w=None, truncation_psi=None):
+        """``w`` (a generator with a mapping network): styles [B, units] in place of latents (``map_latents``); ``truncation_psi``:
+        the truncation trick, w <- w_avg + psi * (w - w_avg), inference only.  ``ema=True``: the averaged generator (``generator_ema=`` of the constructor), inference BatchNorm on its own averaged
         moving statistics.  ``noise`` (a generator with NoiseInjection layers): None draws fresh noise maps, a [B, P] tensor gives
         them, False leaves the noise out (engine.Net.forward)."""
         if ema and self.generator_ema is None:
             raise ValueError("generate_samples(ema=True): this model has no averaged generator (construct it with generator_ema=...)")
         if ema and training:
             raise ValueError("generate_samples(ema=True) runs inference BatchNorm: training=True would overwrite the averaged statistics")
+        G = (self.generator_ema if ema else self.generator).net()
+        style = {} if truncation_psi is None else dict(truncation_psi=truncation_psi)
+        if w is not None:
+            if latents is not None:
+                raise ValueError("generate_samples: either latents or w (the styles, which skip the mapping network), not both")
+            w = self._as_device(w)
+            return G.forward(G.context(int(w.shape[0]), "g"), None, training=training, w=w, **style, **self._noise_args(G, noise))
         if latents is None:
             if self.batch_size is None:
                 self.batch_size = self.hparams.batch_size
             latents = self.latents_batch()
         latents = self._as_device(latents)
-        G = (self.generator_ema if ema else self.generator).net()
         ctx = G.context(int(latents.shape[0]), "g")
-        return G.forward(ctx, latents, training=training, **self._noise_args(G, noise))
+        return G.forward(ctx, latents, training=training, **style, **self._noise_args(G, noise))
 
     # ---- discriminator
     def discriminator_loss(self, reals, fakes, real_scores, fake_scores):
@@ -745,6 +780,7 @@ class WGAN:
         cg = G.context(B, "g")
         G.sync_bn = self.sync_batchnorm
         fakes = G.forward(cg, z, training=True, **self._noise_args(G, self._inj("noise_g")))
+        if G.has_mapping: G.w_avg_update(cg, B * dist.world_size())      # noqa: E701  (the running mean of w: the G-step's batches only)
         chat = D.context(B, "hat")
         s = D.forward(chat, fakes, training=False, augment=self._aug_params("aug_g", ("aug_g",), B)).view(B)
         ds = self._buf("ds_g", (B,))

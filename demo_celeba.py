@@ -136,12 +136,21 @@ def make_parser():
                         help="generator normalisation: BatchNormalization in front of every LeakyReLU (default, the reference's) or a "
                              "PixelNormalization behind it (ProGAN / StyleGAN: per pixel, no variables, no batch statistics; the Dense "
                              "and the hidden convolutions then carry a bias), or 'style': StyleGAN2's modulated convolutions with weight "
-                             "demodulation, the styles taken from the latents (no mapping network)")
+                             "demodulation, the styles taken from the latents or from --mapping-layers")
     parser.add_argument("--normalize-latents", dest="normalize_latents", action="store_true",
                         help="a PixelNormalization of the latent vectors in front of the generator's Dense")
     parser.add_argument("--generator-noise", dest="generator_noise", action="store_true",
                         help="StyleGAN's per-pixel noise inputs: a NoiseInjection (strength * N(0, 1) per pixel, one learned strength per "
                              "layer, initialised to zero) behind every hidden convolution of the generator (needs --generator-norm pixel or style)")
+    parser.add_argument("--mapping-layers", dest="mapping_layers", type=int, default=0, metavar="N",
+                        help="StyleGAN's mapping network in front of the generator: N Dense + LeakyReLU layers z -> w, w the style "
+                             "source of the modulated convolutions (0: off; needs --generator-norm style)")
+    parser.add_argument("--mapping-units", dest="mapping_units", type=int, default=None, metavar="U",
+                        help="width of the mapping network and of w (default: the latent size)")
+    parser.add_argument("--mapping-lr-multiplier", dest="mapping_lr_multiplier", type=float, default=0.01, metavar="M",
+                        help="learning-rate multiplier of the mapping network (with --generator-equalized-lr; without it, it must be 1)")
+    parser.add_argument("--truncation-psi", dest="truncation_psi", type=float, default=None, metavar="P",
+                        help="the truncation trick of the sample grids: w <- w_avg + P * (w - w_avg) (needs --mapping-layers)")
     parser.add_argument("--latent-distribution", dest="latent_distribution", default="uniform", choices=["uniform", "normal"],
                         help="the latents' distribution: uniform on [0, 1) (default, the reference's) or N(0, I) (the ProGAN / StyleGAN "
                              "papers'; what --normalize-latents is meant to normalise)")
@@ -207,9 +216,18 @@ def main(argv=None):
         total_n_examples = 202_599
     config.log_dir = dist.broadcast_object(utils.create_result_subdir(args.results_dir, "celeba") if rank0 else None)
     config.checkpoint_dir = config.log_dir + "/checkpoints"
-    gen = DCGANGenerator(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
-                         normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr,
-                         resample_kernel=args.resample_kernel, noise=args.generator_noise)
+    if args.mapping_layers and args.generator_norm != "style":
+        parser.error("--mapping-layers needs --generator-norm style")
+    if args.truncation_psi is not None and not args.mapping_layers:
+        parser.error("--truncation-psi needs --mapping-layers")
+    gen_kw = dict(upsampling=args.upsampling, spectral_norm=args.generator_spectral_norm, normalization=args.generator_norm,
+                  normalize_latents=args.normalize_latents, equalized_lr=args.generator_equalized_lr,
+                  resample_kernel=args.resample_kernel, noise=args.generator_noise)
+    if args.generator_norm == "style":      # the modulated stack (and its mapping network) is the library's: models.DCGANGenerator
+        gen = blurred_gan.models.DCGANGenerator(arch="celeba128", mapping_layers=args.mapping_layers, mapping_units=args.mapping_units,
+                                                mapping_lr_multiplier=args.mapping_lr_multiplier, **gen_kw)
+    else:
+        gen = DCGANGenerator(**gen_kw)
     disc = DCGANDiscriminator(downsampling=args.downsampling, normalization=args.critic_norm, spectral_norm=args.critic_spectral_norm,
                               minibatch_stddev=args.critic_mbstd, equalized_lr=args.critic_equalized_lr, resample_kernel=args.resample_kernel)
     generator_ema = None
@@ -228,7 +246,7 @@ def main(argv=None):
     if rank0:
         gan.hparams.save_json(os.path.join(config.log_dir, "hyper_parameters.json"))
         gan.config.save_json(os.path.join(config.log_dir, "train_config.json"))
-        cbs = [callbacks.GenerateSampleGridCallback(log_dir=config.log_dir, every_n_examples=5_000), *cbs,
+        cbs = [callbacks.GenerateSampleGridCallback(log_dir=config.log_dir, every_n_examples=5_000, truncation_psi=args.truncation_psi), *cbs,
                callbacks.SaveModelCallback(manager, n=10_000), callbacks.LogMetricsCallback()]
         if args.swd_every_n_examples > 0:        # the reference's SWDMetricCallback, fed from model.images with no host work
             cbs.append(callbacks.SWDMetricCallback(None, num_samples=args.swd_samples, every_n_examples=args.swd_every_n_examples,

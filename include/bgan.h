@@ -359,6 +359,33 @@ int bg_mod_demod_f32(const float* s, const float* Q, float* d, int B, int I, int
 int bg_mod_demod_bwd_f32(const float* d, const float* dd, const float* s, const float* Q, float* dq, float* ds, int B, int I, int O,
                          void* stream);
 
+/* ---- mapping network (StyleGAN's G_mapping, Karras et al. 2019; layers.MappingNetwork): z -> w, fp32 ------------------------------
+ * A stack of skinny Dense layers with the equalised-learning-rate coefficient, the bias multiplier and the LeakyReLU in the epilogue,
+ * the pointwise / bias part of its backward, and the truncation trick.  Everything is deterministic (fixed summation orders, no
+ * atomics: two runs give the same bits), products and sums are rounded separately.  Pointers 4-byte aligned
+ * (BG_ERR_BAD_ALIGNMENT); any size >= 1; a refused call launches nothing.  c, bias_mul, alpha and psi travel by value in the kernel
+ * arguments: a recorded step program replays them with nothing bound.
+ *   dense_lrelu     y[m, n] = act(c * sum_k x[m, k] * W[k, n] + bias_mul * bias[n]), act = LeakyReLU(alpha) (alpha = 1: linear); x
+ *                   [M, K], W [K, N], y [M, N] row-major; bias may be NULL.  The products run on the exact fp32 matrix instruction
+ *                   of bg_gemm_f32; a workgroup owns a BG_DENSE_LRELU tile of y and its four waves share each K-step, their sums
+ *                   added in wave order; the pre-activation is never written.  y must not alias x or W (BG_ERR_UNSUPPORTED).
+ *                   bg_dense_lrelu_plan (host only): {tile rows, tile columns, k per step, workgroups} of a call.
+ *   lrelu_bias_bwd  gp[m, n] = g[m, n] * (y[m, n] > 0 ? 1 : alpha)   (bg_mul_grad_f32's convention: y is the stored OUTPUT, whose sign
+ *                   is the pre-activation's for alpha > 0); gp may alias g, not y (BG_ERR_UNSUPPORTED).  In the same pass
+ *                   dbias[n] = beta * old + scale * sum_m gp[m, n] (beta = 0: old is not read).  float4 units where N % 4 == 0 and
+ *                   g, y, gp are 16-byte aligned, single floats otherwise: no shape or view is refused.  ws:
+ *                   bg_lrelu_bias_bwd_workspace_bytes(M, N) bytes of device scratch (BG_ERR_WORKSPACE).  Two launches.
+ *   truncate        out[b, u] = w_avg[u] + psi * (w[b, u] - w_avg[u]), w_avg [U] in device memory; psi == 1 copies w bit for bit;
+ *                   out may alias w. */
+#define BG_DENSE_LRELU_PLAN_INTS 4
+int bg_dense_lrelu_plan(int M, int N, int K, int* out);
+int bg_dense_lrelu_f32(const float* x, const float* W, const float* bias /* may be NULL */, float* y, int M, int N, int K, float c,
+                       float bias_mul, float alpha, void* stream);
+size_t bg_lrelu_bias_bwd_workspace_bytes(int M, int N);
+int bg_lrelu_bias_bwd_f32(const float* g, const float* y, float* gp, float* dbias, int M, int N, float alpha, float beta, float scale,
+                          void* ws, size_t ws_bytes, void* stream);
+int bg_truncate_f32(const float* w, const float* w_avg, float* out, float psi, int B, int U, void* stream);
+
 /* ---- differentiable augmentation (DiffAugment, Zhao et al. 2020) of the critic's input, NHWC fp32 -----------------------------
  * Per sample an affine map T(x) = L x + k of its [H, W, C] map: colour, then translation, then cutout.  ops_mask: bit 0 colour,
  * bit 1 translation, bit 2 cutout; an absent operation takes its neutral value and does no arithmetic (without colour values are
